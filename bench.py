@@ -10,8 +10,8 @@ memory):
     inlier-support filter (>= 15 inliers, ratio >= 0.1) -> D2H of the compact results.
 value = all pairs pushed through match + verify (every rank) / max-over-ranks step time, with the images already
 resident in HBM when the timed region starts and the results left there (the prompt's measurement rule). The same
-steps from pinned host images to host results (SURVEY.md §8(d)'s PCIe-inclusive unit) are timed as well and reported
-as `value_host_to_host`.
+steps from pinned host images to host results (SURVEY.md §8(d)'s PCIe-inclusive unit) are timed as well under --full
+and reported as `value_host_to_host`.
 
 Workloads:
   --config c2 (default; configs[1] of BASELINE.json): 100 rendered 1920x1080 images, all 4950 pairs. N GPUs share
@@ -32,7 +32,13 @@ Workloads:
 Pairs and images are dealt round-robin over the ranks (pair p to rank p mod N, image i to rank i mod N).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c2-weak|c4|c3-match|c3|c5] [--images n]
-                    [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline figure and what describes
+it. --full adds everything that takes runs of its own: the host-to-host timing, the instrumented per-stage steps and
+the roofline built on them, the matcher certificate and the CPU baseline. --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two builds can be compared
+output for output.
 
 --gpus N > 1 without a launcher starts N fresh rank processes first (gtsfm_amd/launch.py), before anything touches
 a GPU; under `torch.distributed.run` the ranks come from the environment.
@@ -69,6 +75,35 @@ def images_for(n_gpus: int, base: int = 100) -> int:
     while n * (n - 1) // 2 < target:
         n += 1
     return n
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # the files of all ranks together stay under 64 MB
+
+
+def dump_outputs(dirpath: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """Writes the arrays of the last timed step as dirpath/<name>.npy (<name>.rank<r>.npy on ranks r > 0).
+    float32 stays float32, half precision / uint8 / bool become float32, everything else (float64, 32-bit integers)
+    becomes float64, so every value is stored exactly. Each array of each of the `world` ranks may take an equal
+    share of DUMP_BUDGET_BYTES; a larger one is cut to a fixed sample of its rows (leading dimension), drawn with seed
+    0 from the row count alone and kept in order, so equal outputs give equal files. `arrays` holds numpy arrays or torch tensors (sampled on their device)."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(world, 1) // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a)
+            a = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64) if a.dtype.kind == "u" and a.itemsize > 1
+                                                      else a))
+        t = a
+        if t.dim() == 0:
+            t = t.reshape(1)
+        small = t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.bool)
+        row_bytes = max(1, int(np.prod(t.shape[1:]))) * (4 if small else 8)
+        keep = max(1, share // row_bytes)
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        out = (t.detach().cpu().float() if small else t.detach().cpu().double()).numpy()
+        np.save(os.path.join(dirpath, name + (f".rank{rank}" if rank else "") + ".npy"), out)
 
 
 def pmc_traffic(config: str):
@@ -225,7 +260,7 @@ def main_c3(args, world, rank, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, m = step()
+        idx, m = step()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -235,6 +270,13 @@ def main_c3(args, world, rank, dev):
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el.item())
     total_pairs = len(all_pairs)
+    if args.dump_outputs:
+        valid = torch.arange(k, device=dev)[None, :] < m[:, None]  # rows past a pair's count are never written
+        dump_outputs(args.dump_outputs, {"match_idx": torch.where(valid[..., None], idx, -1), "match_count": m}, rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(c3_line(args, world, n_img, k, d, total_pairs, elapsed, m)), flush=True)
+        return
     # shortlist GEMM kernel timed on the call's stream (median of 3)
     lib = native.lib()
     kms = []
@@ -250,7 +292,20 @@ def main_c3(args, world, rank, dev):
     kernel_ms = float(np.median(kms))
     flops = 2.0 * k * k * d * len(mine)  # the distance matrix counted once per pair
     tf = flops / (kernel_ms * 1e-3) / 1e12
-    out = {
+    out = c3_line(args, world, n_img, k, d, total_pairs, elapsed, m)
+    out["roofline"] = {"bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                       "frac": round(tf / MFMA_F16_PEAK_TFLOPS, 4), "traffic": None,
+                       "kernel": "fl_shortlist_kernel<16> (one launch per step)", "kernel_ms": round(kernel_ms, 3),
+                       "work": "2*K1*K2*D flop per pair (the kernel computes the matrix once per side: 2x this)"}
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = c3_cpu_baseline(desc)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def c3_line(args, world, n_img, k, d, total_pairs, elapsed, m) -> dict:
+    """The c3-match result line without what --full adds."""
+    return {
         "metric": "matched image-pairs/sec (all-pairs SuperPoint-descriptor matching, configs[2])",
         "value": round(total_pairs / (elapsed / args.steps), 2), "unit": "image-pairs/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -260,15 +315,7 @@ def main_c3(args, world, rank, dev):
                                f"pairs, mutual NN + ratio {RATIO}", "images": n_img, "pairs": total_pairs, "kpts": k,
                    "parallelism": f"pair blocks x{world}"},
         "mean_matches": round(float(m.float().mean().item()), 1),
-        "roofline": {"bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(tf / MFMA_F16_PEAK_TFLOPS, 4), "traffic": None,
-                     "kernel": "fl_shortlist_kernel<16> (one launch per step)", "kernel_ms": round(kernel_ms, 3),
-                     "work": "2*K1*K2*D flop per pair (the kernel computes the matrix once per side: 2x this)"},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = c3_cpu_baseline(desc)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
 
 
 
@@ -323,18 +370,29 @@ def main_netvlad(args, world, rank, dev):
 
     for _ in range(args.warmup):
         step()
-    elapsed = timed_loop(step, args.steps, world, dev)
-    # the descriptor stage alone, timed with events on the compute stream
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for s0 in range(0, len(mine), g):
-        hip.netvlad_describe(imgs[s0: s0 + g], w, workspace=ws)
-    ev[1].record()
-    torch.cuda.synchronize()
-    desc_ms = ev[0].elapsed_time(ev[1])
-    flop = len(mine) * vgg16_conv_flop(H, W)
-    tf = flop / (desc_ms * 1e-3) / 1e12
-    split_peak = MFMA_F16_PEAK_TFLOPS / 6.0
+    last = []
+
+    def timed_step():
+        last[:] = [step()]
+
+    elapsed = timed_loop(timed_step, args.steps, world, dev)
+    if args.dump_outputs:
+        arrays = {"descriptors": out}
+        if last[0] is not None:
+            pairs, row_count = last[0]
+            valid = torch.arange(pairs.shape[1], device=dev)[None, :] < row_count[:, None]
+            arrays.update(retrieval_pairs=torch.where(valid[..., None], pairs, -1), retrieval_row_count=row_count)
+        dump_outputs(args.dump_outputs, arrays, rank, world)
+    desc_ms = None
+    if args.full:
+        # the descriptor stage alone, timed with events on the compute stream
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for s0 in range(0, len(mine), g):
+            hip.netvlad_describe(imgs[s0: s0 + g], w, workspace=ws)
+        ev[1].record()
+        torch.cuda.synchronize()
+        desc_ms = ev[0].elapsed_time(ev[1])
     value = n_img / (elapsed / args.steps)
     out_line = {
         "metric": "NetVLAD global descriptors + retrieval pairs, images/sec (f3)",
@@ -346,14 +404,19 @@ def main_netvlad(args, world, rank, dev):
         "config": {"workload": f"f3: {n_img} synthetic {W}x{H} images -> NetVLAD 4096-D descriptors -> "
                                "similarity + top-20 pairs (min_score 0.3)", "images": n_img,
                    "parallelism": f"images x{world}"},
-        "roofline": {"bound": "mfma", "achieved": round(tf, 1), "peak": round(split_peak, 1), "unit": "TFLOP/s",
-                     "frac": round(tf / split_peak, 4), "traffic": None, "kernel_ms": round(desc_ms, 3),
-                     "kernel": "NetVLAD descriptor launches (conv3_kernel x 12 + input conv + VLAD + whitening)",
-                     "work": "VGG16 features[:-2] conv flop %.1f GFLOP per image (2 per MAC) over %d images; convs "
-                             "as fp32-accurate bf16x3 split products (peak = dense bf16 MFMA / 6)"
-                             % (vgg16_conv_flop(H, W) / 1e9, len(mine))},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        flop = len(mine) * vgg16_conv_flop(H, W)
+        tf = flop / (desc_ms * 1e-3) / 1e12
+        split_peak = MFMA_F16_PEAK_TFLOPS / 6.0
+        out_line["roofline"] = {
+            "bound": "mfma", "achieved": round(tf, 1), "peak": round(split_peak, 1), "unit": "TFLOP/s",
+            "frac": round(tf / split_peak, 4), "traffic": None, "kernel_ms": round(desc_ms, 3),
+            "kernel": "NetVLAD descriptor launches (conv3_kernel x 12 + input conv + VLAD + whitening)",
+            "work": "VGG16 features[:-2] conv flop %.1f GFLOP per image (2 per MAC) over %d images; convs "
+                    "as fp32-accurate bf16x3 split products (peak = dense bf16 MFMA / 6)"
+                    % (vgg16_conv_flop(H, W) / 1e9, len(mine))}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import deep
 
         torch.set_num_threads(16)
@@ -595,7 +658,7 @@ def main_frontend(args, info, config: str):
         rank, world = args.emulate_rank, args.emulate_world
     elif args.pair_limit:
         raise SystemExit("--pair-limit only applies to --emulate-world runs")
-    want_baseline = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_baseline = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if config == "c1":
         all_imgs, intrinsics = lund_door_c1()
         n_img, scaling = len(all_imgs), "strong"
@@ -675,15 +738,92 @@ def main_frontend(args, info, config: str):
     fe = AllPairsFrontEnd(host_images, intrinsics, n_img, rank, world, dev, cfg, kernels=kernels, exchange=exchange,
                           pair_limit=args.pair_limit or None)
 
+    fe.dev_images.copy_(fe.host_images)  # the timed steps find the images in HBM, whatever --warmup is
     for _ in range(args.warmup):
-        res = fe.step()
+        fe.step()
     tworld = 1 if emulate else world  # the emulated job has one process
-    elapsed = timed_steps(fe, args.steps, False, tworld, dev)
+    if args.full:
+        elapsed = timed_steps(fe, args.steps, False, tworld, dev)
     elapsed_res = timed_steps(fe, args.steps, True, tworld, dev)
     # `value` is the device-resident figure (inputs in HBM when the timed region starts); the host-to-host figure of
-    # SURVEY.md §8(d) (PCIe copies inside the step) is reported beside it, never as value
+    # SURVEY.md §8(d) (PCIe copies inside the step) is reported beside it under --full, never as value
     ms_per_step = elapsed_res / args.steps * 1e3
     value = fe.total_pairs / (elapsed_res / args.steps)
+    # what the last timed step computed, fetched from the device as a host-to-host step returns it
+    res = fe._to_host()
+    if args.dump_outputs:
+        kp_valid = np.arange(res.kp_xy.shape[1])[None, :] < res.kp_count[:, None]  # rows past an image's count: -1
+        dump_outputs(args.dump_outputs, {
+            "pairs": res.pairs, "R": res.R, "t": res.t, "status": res.status, "n_inliers": res.n_inliers,
+            "n_matches": res.n_matches, "isp_ok": res.isp_ok, "offsets": res.offsets, "v_corr": res.v_corr,
+            "kp_xy": np.where(kp_valid[..., None], res.kp_xy, np.float32(-1)), "kp_count": res.kp_count},
+            *((0, 1) if emulate else (rank, world)))
+    n_ok = torch.tensor([float(res.isp_ok.sum())], dtype=torch.float64, device=dev)
+    n_inl_rows = torch.tensor([float(len(res.v_corr))], dtype=torch.float64, device=dev)
+    if world > 1 and not emulate:
+        torch.distributed.all_reduce(n_ok)
+        torch.distributed.all_reduce(n_inl_rows)
+    M_p = fe.stats["n_matches"].double() if "n_matches" in fe.stats else torch.zeros(0)
+    wl = {"c1": "C1", "c4": "C4", "c3": "C3", "c5": "C5 slice"}.get(config, "C2")
+    if deep:
+        desc = (f"{wl}: {n_img} synthetic {W}x{H} images, all {fe.total_pairs} pairs, SuperPoint {kpts} kpts/img + "
+                + ("SuperGlue 18 layers / 20 Sinkhorn iterations" if config == "c5" else
+                   f"TwoWayMatcher ratio {RATIO} (F16_RERANK)") + f", 5-pt RANSAC {THRESH_PX}px + inlier support")
+        dtype = ("u8 image / fp32-accurate bf16x3-MFMA SuperPoint / " + ("fp32-accurate bf16x3-MFMA SuperGlue"
+                                                                      if config == "c5" else
+                 "fp16-MFMA shortlist + fp32 exact re-rank") + " / fp64 RANSAC solver")
+        data = ("synthetic (rendered textured room, seeds 0/1/2" + ("; 1 m strafe path" if config == "c3" else "")
+                + "); seeded random network weights with " +
+                ("the plain seeded SuperPoint descriptor head (tests/superpoint_weights.py seed 0, not whitened)"
+                 if head is False else "a whitened SuperPoint descriptor head "
+                 "(tests/golden/make_superpoint_whitening.py" + (" --c3" if config == "c3" else "") + ")"))
+    else:
+        desc = (f"{wl}: {n_img} {'Lund Door' if config == 'c1' else 'synthetic'} {W}x{H} images, all "
+                f"{fe.total_pairs} pairs, SIFT {kpts} kpts/img, ratio {RATIO}, 5-pt RANSAC {THRESH_PX}px"
+                + (" + two-view BA" if args.ba else "") + " + inlier support")
+        dtype = "u8 image / fp32 pyramid / fp16-MFMA exact-int distances / fp64 RANSAC solver"
+        data = ("the reference's Lund Door images (tests/data/set1_lund_door)" if config == "c1" else
+                "synthetic (rendered textured room, seeds 0/1/2)")
+    out = {
+        "metric": "verified image-pairs/sec (all-pairs front-end), N images @ 2048 kpts/img",
+        "value": round(value, 2),
+        "unit": "image-pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": dtype,
+        "data": data,
+        "config": {"workload": desc, "images": n_img, "pairs": fe.total_pairs, "kpts": kpts,
+                   "parallelism": f"pair blocks x{world}",
+                   "world_size": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1},
+        "pairs_passing_isp": int(n_ok.item()),
+        "verified_rows": int(n_inl_rows.item()),
+        "mean_putatives": round(float(M_p.mean()), 1) if len(M_p) else 0.0,
+        "parity": parity_statement(config, args.ba),
+    }
+    if emulate:
+        # a per-rank measurement, not a scaling curve: value = this rank's pairs per second of its own step
+        out["metric"] = "per-rank verified image-pairs/sec (one rank's share of an N-GPU job, emulated on one GPU)"
+        out["value"] = round(fe.P / (elapsed_res / args.steps), 2)
+        out["n_gpus"] = 1
+        out["scaling"] = "per-rank"
+        out["emulated"] = {
+            "rank": rank, "world": world, "rank_images": fe.n_local, "rank_pairs": fe.P, "job_pairs": fe.total_pairs,
+            "implied_job_pairs_per_s_if_ranks_equal": None if args.pair_limit else
+            round(fe.total_pairs / (elapsed_res / args.steps), 2),
+            "pair_limit": args.pair_limit or None,
+            "note": "rank `rank` of a `world`-rank job run alone on one GPU: its images extracted, the exchange's "
+                    "packing + the gathered buffer's write (the other ranks' blocks extracted untimed beforehand; "
+                    "the xGMI transfer of the all-gather is NOT included), its pair share (every N-th pair) matched, "
+                    "verified and compacted"}
+    if not args.full:
+        if rank == 0 or emulate:
+            print(json.dumps(out), flush=True)
+        return
 
     # instrumented steps: per-phase HIP events on the compute / copy streams; the matcher kernel's own events
     # (the distance GEMM, or F16_RERANK's shortlist GEMM) through gtsfm_match_set_kernel_events
@@ -720,8 +860,6 @@ def main_frontend(args, info, config: str):
         st = {}
         hip.match_pairs(fe.feats.desc, fe.feats.count, fe.pairs_dev, RATIO, native.GTSFM_MATCH_F16_RERANK, stats=st)
         certificate = {k: (round(v, 5) if isinstance(v, float) else v) for k, v in st.items()}
-    n_ok = torch.tensor([float(res.isp_ok.sum())], dtype=torch.float64, device=dev)
-    n_inl_rows = torch.tensor([float(len(res.v_corr))], dtype=torch.float64, device=dev)
     # per-stage algorithmic work of this rank
     kc = kc_all
     kc[mine] = res.kp_count
@@ -730,8 +868,6 @@ def main_frontend(args, info, config: str):
         t = torch.from_numpy(kc).to(dev)
         torch.distributed.all_reduce(t)
         kc = t.cpu().numpy()
-        torch.distributed.all_reduce(n_ok)
-        torch.distributed.all_reduce(n_inl_rows)
     pr = fe.my_pairs
     a_last, b_last = fe.pchunks[-1]
     pl = pr[a_last:b_last]  # the kernel events end on the LAST pair chunk's launch: its pairs are that launch's work
@@ -836,69 +972,15 @@ def main_frontend(args, info, config: str):
                                             f"{k} {v['hbm_bytes_per_launch'] / 1e6:.1f} MB x {v['launches']}"
                                             for k, v in pmc["kernels"].items() if k != "fl_shortlist_kernel"))
         roof["stages"] = {"extract": ex_stage, "match": match_stage, "verify": verify_stage}
-    wl = {"c1": "C1", "c4": "C4", "c3": "C3", "c5": "C5 slice"}.get(config, "C2")
-    if deep:
-        desc = (f"{wl}: {n_img} synthetic {W}x{H} images, all {fe.total_pairs} pairs, SuperPoint {kpts} kpts/img + "
-                + ("SuperGlue 18 layers / 20 Sinkhorn iterations" if config == "c5" else
-                   f"TwoWayMatcher ratio {RATIO} (F16_RERANK)") + f", 5-pt RANSAC {THRESH_PX}px + inlier support")
-        dtype = ("u8 image / fp32-accurate bf16x3-MFMA SuperPoint / " + ("fp32-accurate bf16x3-MFMA SuperGlue"
-                                                                      if config == "c5" else
-                 "fp16-MFMA shortlist + fp32 exact re-rank") + " / fp64 RANSAC solver")
-        data = ("synthetic (rendered textured room, seeds 0/1/2" + ("; 1 m strafe path" if config == "c3" else "")
-                + "); seeded random network weights with " +
-                ("the plain seeded SuperPoint descriptor head (tests/superpoint_weights.py seed 0, not whitened)"
-                 if head is False else "a whitened SuperPoint descriptor head "
-                 "(tests/golden/make_superpoint_whitening.py" + (" --c3" if config == "c3" else "") + ")"))
-    else:
-        desc = (f"{wl}: {n_img} {'Lund Door' if config == 'c1' else 'synthetic'} {W}x{H} images, all "
-                f"{fe.total_pairs} pairs, SIFT {kpts} kpts/img, ratio {RATIO}, 5-pt RANSAC {THRESH_PX}px"
-                + (" + two-view BA" if args.ba else "") + " + inlier support")
-        dtype = "u8 image / fp32 pyramid / fp16-MFMA exact-int distances / fp64 RANSAC solver"
-        data = ("the reference's Lund Door images (tests/data/set1_lund_door)" if config == "c1" else
-                "synthetic (rendered textured room, seeds 0/1/2)")
-    out = {
-        "metric": "verified image-pairs/sec (all-pairs front-end), N images @ 2048 kpts/img",
-        "value": round(value, 2),
-        "unit": "image-pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": dtype,
-        "data": data,
-        "config": {"workload": desc, "images": n_img, "pairs": fe.total_pairs, "kpts": kpts,
-                   "parallelism": f"pair blocks x{world}",
-                   "world_size": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1},
+    out.update({
         "value_host_to_host": round(fe.total_pairs / (elapsed / args.steps), 2),
         "ms_per_step_host_to_host": round(elapsed / args.steps * 1e3, 3),
-        "pairs_passing_isp": int(n_ok.item()),
-        "verified_rows": int(n_inl_rows.item()),
-        "mean_putatives": round(float(M_p.mean()), 1) if len(M_p) else 0.0,
         "stage_ms": st_res,
         "stage_ms_host_to_host": st_host,
         "roofline": roof,
-        "parity": parity_statement(config, args.ba),
-    }
+    })
     if certificate is not None:
         out["matcher_certificate"] = certificate
-    if emulate:
-        # a per-rank measurement, not a scaling curve: value = this rank's pairs per second of its own step
-        out["metric"] = "per-rank verified image-pairs/sec (one rank's share of an N-GPU job, emulated on one GPU)"
-        out["value"] = round(fe.P / (elapsed_res / args.steps), 2)
-        out["n_gpus"] = 1
-        out["scaling"] = "per-rank"
-        out["emulated"] = {
-            "rank": rank, "world": world, "rank_images": fe.n_local, "rank_pairs": fe.P, "job_pairs": fe.total_pairs,
-            "implied_job_pairs_per_s_if_ranks_equal": None if args.pair_limit else
-            round(fe.total_pairs / (elapsed_res / args.steps), 2),
-            "pair_limit": args.pair_limit or None,
-            "note": "rank `rank` of a `world`-rank job run alone on one GPU: its images extracted, the exchange's "
-                    "packing + the gathered buffer's write (the other ranks' blocks extracted untimed beforehand; "
-                    "the xGMI transfer of the all-gather is NOT included), its pair share (every N-th pair) matched, "
-                    "verified and compacted"}
     if want_baseline:
         if deep:
             out["cpu_baseline"] = deep_cpu_baseline(baseline_images, intrinsics, n_img, kpts, sp_sd, sg_sd,
@@ -925,7 +1007,13 @@ def main():
     ap.add_argument("--extract-first", type=int, default=0)
     ap.add_argument("--resident-chunk", type=int, default=0)
     ap.add_argument("--pair-chunk", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the host-to-host timing, the instrumented per-stage "
+                         "steps and their roofline, the matcher certificate and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB in all; larger arrays as a fixed seeded sample of their rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="time the CPU baseline on the whole workload (C2: ~100 s on 16 threads) instead of a sample")
     ap.add_argument("--c3-head", choices=("c3", "plain"), default="c3",
@@ -943,6 +1031,10 @@ def main():
     ap.add_argument("--launch-probe", action="store_true",
                     help="each rank joins a gloo group, prints what it sees and exits (tests the launch path on CPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cpu_baseline_full and not args.full:
+        ap.error("--cpu-baseline-full belongs to --full runs")
 
     if args.gpus > 1 and launch.launched_world() == 1:
         # no launcher: start the ranks now, before this process touches a GPU, and exit with their status

@@ -3,7 +3,7 @@
 Runs AllPairsFrontEnd on the C2 scene (100 rendered 1080p images, 4950 pairs) with the library named by
 GTSFM_HIP_LIB (default: the in-tree product build), prints the median per-stage milliseconds of 3 instrumented
 device-resident steps as one JSON line, and compares the per-pair verifier results with a reference run saved by the
-first invocation (gpurun_out/verify_ref.npz): status, inlier counts, hypothesis counts and R must match, so a
+first invocation (verify_ref.npz in $OUT, default bench_out/): status, inlier counts, hypothesis counts and R must match, so a
 variant that changes results is flagged.
 
     for v in build_var/libgtsfm_hip_*.so; do GTSFM_HIP_LIB=$v python tools/verify_bench.py; done
@@ -38,7 +38,7 @@ def main():
         rows.append(fe.stage_ms())
     st = {k: round(float(np.median([r[k] for r in rows])), 3) for k in rows[0]}
     n_hyp = fe.stats["n_hyp"].cpu().numpy()
-    ref_path = os.path.join(REPO, "gpurun_out", "verify_ref.npz")
+    ref_path = os.path.join(os.environ.get("OUT") or os.path.join(REPO, "bench_out"), "verify_ref.npz")
     cur = dict(status=res.status, n_inliers=res.n_inliers, n_hyp=n_hyp, R=res.R)
     same = None
     if os.path.exists(ref_path):
