@@ -117,6 +117,9 @@ def calibration_params(cal) -> np.ndarray:
 
 
 def rotation_matrix(R) -> np.ndarray:
+    """3x3 float64 matrix of a Rot3 (gtsam's or the stand-in: anything with .matrix()) or of a 3x3 array."""
+    if isinstance(R, np.ndarray):
+        return np.asarray(R, dtype=np.float64).reshape(3, 3)
     return np.asarray(R.matrix(), dtype=np.float64)
 
 

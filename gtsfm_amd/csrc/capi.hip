@@ -9,6 +9,7 @@ extern "C" {
 //       reject more argument shapes with GTSFM_ERR_ARG
 // 4.01: gtsfm_netvlad_* added (NetVLAD global descriptor)
 // 4.02: gtsfm_match_rerank_stats added (F16_RERANK certificate counts)
+// 4.03: gtsfm_viewgraph_* added (cycle-consistent rotation view-graph filter)
 int gtsfm_hip_abi_version(void) { return GTSFM_HIP_ABI_VERSION; }
 
 const char* gtsfm_hip_target(void) { return "gfx950"; }

@@ -565,3 +565,37 @@ def netvlad_describe(images: torch.Tensor, weights: torch.Tensor, whiten: bool =
                                  _ptr(ws), ws.numel(), native.stream_handle(stream))
     native.check(rc, "gtsfm_netvlad_batched")
     return desc, vlad
+
+
+def viewgraph_cycle_filter(edges: torch.Tensor, R: torch.Tensor, valid: Optional[torch.Tensor], n_img: int,
+                           criterion: int, error_threshold_deg: float, stream: Optional[torch.cuda.Stream] = None,
+                           workspace: Optional[torch.Tensor] = None, want_total: bool = True,
+                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Cycle-consistent rotation filter over a view graph (gtsfm_viewgraph_cycle_filter).
+
+    edges: (E, 2) int32 (i1 < i2 < n_img, each pair once); R: (E, 3, 3) float64 i2Ri1; valid: (E,) uint8 or None.
+    Returns (keep (E,) uint8, agg_error_deg (E,) float64, n_triplets (E,) int32, total_triplets (1,) int64 or None),
+    all on the device and in input order."""
+    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous()
+    E = edges.shape[0]
+    assert tuple(edges.shape) == (E, 2)
+    assert R.is_cuda and R.dtype == torch.float64 and R.is_contiguous() and R.numel() == 9 * E
+    if valid is not None:
+        assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == E
+    dev = edges.device
+    agg = torch.empty(E, dtype=torch.float64, device=dev)
+    n_trip = torch.empty(E, dtype=torch.int32, device=dev)
+    keep = torch.empty(E, dtype=torch.uint8, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev) if want_total else None
+    L = native.lib()
+    need = L.gtsfm_viewgraph_workspace_bytes(int(n_img), E)
+    if E > 0 and need == 0:
+        raise native.NativeError(f"gtsfm_viewgraph_cycle_filter supports 1..{native.VG_MAX_IMAGES} images, got {n_img}")
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_viewgraph_cycle_filter(_ptr(edges), _ptr(R), _ptr(valid), int(n_img), E, int(criterion),
+                                        float(error_threshold_deg), _ptr(ws), ws.numel(), _ptr(agg), _ptr(n_trip),
+                                        _ptr(keep), _ptr(total), native.stream_handle(stream))
+    native.check(rc, "gtsfm_viewgraph_cycle_filter")
+    return keep, agg, n_trip, total

@@ -28,7 +28,7 @@ c_size_t = ctypes.c_size_t
 c_uint64 = ctypes.c_uint64
 
 # Mirrors include/gtsfm_hip.h
-ABI_VERSION = 402  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
+ABI_VERSION = 403  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
 GTSFM_OK = 0
 GTSFM_ERR_ARG = -1
 GTSFM_ERR_HIP = -2
@@ -48,6 +48,9 @@ BA2_STATUS_OK = 0
 BA2_STATUS_NO_TRACKS = 1
 BA2_STATUS_NONE_VALID = 2
 BA2_STATUS_NOT_RUN = 3
+GTSFM_VG_MIN_EDGE_ERROR = 0
+GTSFM_VG_MEDIAN_EDGE_ERROR = 1
+VG_MAX_IMAGES = 8192  # gtsfm_viewgraph_cycle_filter's n_img ceiling
 
 # (name, restype, argtypes) of every symbol declared in include/gtsfm_hip.h
 SIGNATURES = {
@@ -122,6 +125,12 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_viewgraph_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gtsfm_viewgraph_cycle_filter": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p],
     ),
 }
 

@@ -20,6 +20,10 @@
  *   gtsfm_retrieval_*       <- gtsfm/retriever/netvlad_retriever.py:77-228 (similarity blocks + pairs_from_score_matrix)
  *   gtsfm_netvlad_*         <- gtsfm/frontend/global_descriptor/netvlad_global_descriptor.py:27-46 describe +
  *                              thirdparty/hloc/netvlad.py:28-71 (NetVLADLayer), :160-191 (NetVLAD.forward)
+ *   gtsfm_viewgraph_*       <- gtsfm/view_graph_estimator/cycle_consistent_rotation_estimator.py:49-152
+ *                              CycleConsistentRotationViewGraphEstimator.run + gtsfm/utils/graph.py:100-135
+ *                              extract_cyclic_triplets_from_edges + gtsfm/utils/geometry_comparisons.py:355-370
+ *                              compute_cyclic_rotation_error
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -41,7 +45,7 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
-#define GTSFM_HIP_ABI_VERSION 402
+#define GTSFM_HIP_ABI_VERSION 403
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
 const char* gtsfm_hip_target(void);
@@ -336,6 +340,38 @@ size_t gtsfm_netvlad_workspace_bytes(int n, int H, int W);
 
 int gtsfm_netvlad_batched(const uint8_t* d_images, int n, int H, int W, int C, const float* d_weights, int whiten,
                           float* d_vlad, float* d_desc, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * View graph: cycle-consistent rotation filter. Replaces CycleConsistentRotationViewGraphEstimator.run
+ * (gtsfm/view_graph_estimator/cycle_consistent_rotation_estimator.py:78-152), with the triplet extraction
+ * (gtsfm/utils/graph.py:100-135) and the cycle error (gtsfm/utils/geometry_comparisons.py:355-370) it calls.
+ * Edges d_edges[n_edges][2] = (i1, i2) image indices with i1 < i2 < n_img, each pair at most once, in any order (sorted
+ * by (i1, i2), as the front-end emits them, is the cache-friendly order); d_R[n_edges][9] row-major i2Ri1;
+ * d_valid[n_edges] (0 = the edge is absent from the graph: it is no adjacency and gets no result) or NULL (all valid).
+ * An edge whose indices are out of range or not ordered is treated as invalid.
+ * A triplet is three images i0 < i1 < i2 whose three edges are all valid. Its cycle error is the rotation angle in
+ * degrees of M = R(i0,i2)^T R(i1,i2) R(i0,i1), computed in fp64 as
+ *   atan2(|(M32 - M23, M13 - M31, M21 - M12)| / 2, (tr M - 1) / 2)
+ * (equal to the reference's scipy as_rotvec norm to 1e-13 degrees, and well-conditioned near 0, where acos is not).
+ * Per edge, over every triplet that contains it: d_n_triplets = their number, d_agg_error_deg = np.amin
+ * (GTSFM_VG_MIN_EDGE_ERROR) or np.median (GTSFM_VG_MEDIAN_EDGE_ERROR; exact, an even count gives the mean of the two
+ * middle values) of their cycle errors, NaN when one of them is NaN, and NaN when the edge is invalid or in no triplet;
+ * d_keep = 1 iff n_triplets > 0 and the aggregate < error_threshold_deg (the reference's ERROR_THRESHOLD is 7.0).
+ * d_total_triplets[0] (may be NULL) = the number of distinct triplets. Results are bit-identical from run to run.
+ * n_img <= 8192 (the workspace holds a dense n_img x n_img edge lookup: 4 n_img^2 + n_img^2 / 8 bytes; an edge may
+ * have up to n_img - 2 triplets and all of them are aggregated): GTSFM_ERR_ARG above it, and for a negative size, an
+ * unknown criterion or a workspace smaller than the query's answer. n_edges == 0 returns GTSFM_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define GTSFM_VG_MIN_EDGE_ERROR 0
+#define GTSFM_VG_MEDIAN_EDGE_ERROR 1
+
+/* 0 when n_edges == 0 (or the shape is unsupported). */
+size_t gtsfm_viewgraph_workspace_bytes(int n_img, int n_edges);
+
+int gtsfm_viewgraph_cycle_filter(const int* d_edges, const double* d_R, const uint8_t* d_valid, int n_img, int n_edges,
+                                 int criterion, double error_threshold_deg, void* d_workspace, size_t workspace_bytes,
+                                 double* d_agg_error_deg, int* d_n_triplets, uint8_t* d_keep,
+                                 unsigned long long* d_total_triplets, void* stream);
 
 #ifdef __cplusplus
 }
