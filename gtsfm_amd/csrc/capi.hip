@@ -10,6 +10,7 @@ extern "C" {
 // 4.01: gtsfm_netvlad_* added (NetVLAD global descriptor)
 // 4.02: gtsfm_match_rerank_stats added (F16_RERANK certificate counts)
 // 4.03: gtsfm_viewgraph_* added (cycle-consistent rotation view-graph filter)
+// 4.04: gtsfm_tracks_* added (2D feature tracks from verified correspondences, union-find)
 int gtsfm_hip_abi_version(void) { return GTSFM_HIP_ABI_VERSION; }
 
 const char* gtsfm_hip_target(void) { return "gfx950"; }

@@ -599,3 +599,64 @@ def viewgraph_cycle_filter(edges: torch.Tensor, R: torch.Tensor, valid: Optional
                                         _ptr(keep), _ptr(total), native.stream_handle(stream))
     native.check(rc, "gtsfm_viewgraph_cycle_filter")
     return keep, agg, n_trip, total
+
+
+def tracks_from_matches(pairs: torch.Tensor, offsets: torch.Tensor, v_corr: torch.Tensor, kp_count: torch.Tensor,
+                        kmax: int, valid: Optional[torch.Tensor] = None, kp_xy: Optional[torch.Tensor] = None,
+                        n_rows: Optional[int] = None, track_cap: Optional[int] = None, meas_cap: Optional[int] = None,
+                        stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                        out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """2D feature tracks of a set of verified correspondences (gtsfm_tracks_from_matches).
+
+    pairs: (P, 2) int32 image indices; offsets: (P + 1,) int32 and v_corr: (rows, 2) int32 holding uint32 keypoint
+    indices, the CSR compact_verified returns; kp_count: (n_img,) int32; valid: (P,) uint8 or None; kp_xy:
+    (n_img, kmax, 2) float32 or None. n_rows: the rows of v_corr that may be read (default: all of v_corr; the rows in
+    use are offsets[P], which stays on the device). track_cap / meas_cap default to min(2 * n_rows, n_img * kmax), which
+    always suffices. `out` = (track_offsets, track_img, track_kp, track_uv) reuses the caller's buffers.
+    Returns (track_offsets (track_cap + 1,) int32, track_img (meas_cap,) int32, track_kp (meas_cap,) int32, track_uv
+    (meas_cap, 2) float32 or None, stats (5,) int64 = n_tracks, n_measurements, n_components, n_erroneous, n_bad_rows),
+    all on the device; entries past the counts in stats are not written. Tracks are in canonical order: ascending
+    smallest (image, keypoint), measurements ascending inside a track."""
+    assert pairs.is_cuda and pairs.dtype == torch.int32 and pairs.is_contiguous()
+    P = pairs.shape[0]
+    assert tuple(pairs.shape) == (P, 2)
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= P + 1
+    assert v_corr.is_cuda and v_corr.dtype == torch.int32 and v_corr.is_contiguous() and v_corr.dim() == 2
+    assert v_corr.shape[1] == 2
+    assert kp_count.is_cuda and kp_count.dtype == torch.int32 and kp_count.is_contiguous()
+    n_img, kmax = kp_count.numel(), int(kmax)
+    if valid is not None:
+        assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == P
+    if kp_xy is not None:
+        assert kp_xy.is_cuda and kp_xy.dtype == torch.float32 and kp_xy.is_contiguous()
+        assert kp_xy.numel() == n_img * kmax * 2
+    n_rows = v_corr.shape[0] if n_rows is None else int(n_rows)
+    assert 0 <= n_rows <= v_corr.shape[0]
+    dev = pairs.device
+    enough = min(2 * n_rows, n_img * kmax)
+    track_cap = enough if track_cap is None else int(track_cap)
+    meas_cap = enough if meas_cap is None else int(meas_cap)
+    if out is not None:
+        t_off, t_img, t_kp, t_uv = out
+        assert t_off.numel() >= track_cap + 1 and t_img.numel() >= meas_cap and t_kp.numel() >= meas_cap
+        assert t_uv is None or t_uv.numel() >= 2 * meas_cap
+    else:
+        t_off = torch.empty(track_cap + 1, dtype=torch.int32, device=dev)
+        t_img = torch.empty(meas_cap, dtype=torch.int32, device=dev)
+        t_kp = torch.empty(meas_cap, dtype=torch.int32, device=dev)
+        t_uv = torch.empty((meas_cap, 2), dtype=torch.float32, device=dev) if kp_xy is not None else None
+    stats = torch.empty(5, dtype=torch.int64, device=dev)
+    L = native.lib()
+    need = L.gtsfm_tracks_workspace_bytes(n_img, kmax, P, n_rows)
+    if P > 0 and n_rows > 0 and need == 0:
+        raise native.NativeError(f"gtsfm_tracks_from_matches needs 0 < n_img * kmax < 2^31, got {n_img} x {kmax}")
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_tracks_from_matches(_ptr(pairs), _ptr(offsets), _ptr(v_corr), _ptr(valid), P, n_rows, _ptr(kp_count),
+                                     _ptr(kp_xy), n_img, kmax, _ptr(ws), ws.numel(), _ptr(t_off), track_cap,
+                                     _ptr(t_img), _ptr(t_kp), _ptr(t_uv), meas_cap, _ptr(stats),
+                                     native.stream_handle(stream))
+    native.check(rc, "gtsfm_tracks_from_matches")
+    return t_off, t_img, t_kp, t_uv, stats

@@ -26,9 +26,10 @@ c_double = ctypes.c_double
 c_float = ctypes.c_float
 c_size_t = ctypes.c_size_t
 c_uint64 = ctypes.c_uint64
+c_longlong = ctypes.c_longlong
 
 # Mirrors include/gtsfm_hip.h
-ABI_VERSION = 403  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
+ABI_VERSION = 404  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
 GTSFM_OK = 0
 GTSFM_ERR_ARG = -1
 GTSFM_ERR_HIP = -2
@@ -131,6 +132,12 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p],
+    ),
+    "gtsfm_tracks_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_longlong]),
+    "gtsfm_tracks_from_matches": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p,
+         c_size_t, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p],
     ),
 }
 

@@ -24,6 +24,9 @@
  *                              CycleConsistentRotationViewGraphEstimator.run + gtsfm/utils/graph.py:100-135
  *                              extract_cyclic_triplets_from_edges + gtsfm/utils/geometry_comparisons.py:355-370
  *                              compute_cyclic_rotation_error
+ *   gtsfm_tracks_*          <- gtsfm/data_association/dsf_tracks_estimator.py:56-85 DsfTracksEstimator.run,
+ *                              cpp_dsf_tracks_estimator.py:63-74 (gtsam tracksFromPairwiseMatches) and
+ *                              gtsfm/common/sfm_track.py:105-112 validate_unique_cameras
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -45,7 +48,7 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
-#define GTSFM_HIP_ABI_VERSION 403
+#define GTSFM_HIP_ABI_VERSION 404
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
 const char* gtsfm_hip_target(void);
@@ -372,6 +375,49 @@ int gtsfm_viewgraph_cycle_filter(const int* d_edges, const double* d_R, const ui
                                  int criterion, double error_threshold_deg, void* d_workspace, size_t workspace_bytes,
                                  double* d_agg_error_deg, int* d_n_triplets, uint8_t* d_keep,
                                  unsigned long long* d_total_triplets, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * 2D feature tracks from verified correspondences (disjoint-set forest). Replaces DsfTracksEstimator.run
+ * (gtsfm/data_association/dsf_tracks_estimator.py:56-85: one dsf.merge per correspondence row, dsf.sets(), and the
+ * unique-camera filter of gtsfm/common/sfm_track.py:105-112) and CppDsfTracksEstimator.run
+ * (cpp_dsf_tracks_estimator.py:63-74), the step get_2d_tracks (gtsfm/multi_view_optimizer.py:195-199) runs on the
+ * view graph's correspondences.
+ * Inputs: d_pairs[n_pairs][2] = (i1, i2) image indices in any order, i1 == i2 and repeated pairs allowed;
+ * d_offsets[n_pairs + 1] and d_v_corr[..][2] = (k1, k2) uint32, the CSR gtsfm_compact_verified writes (pair p owns rows
+ * offsets[p] .. offsets[p + 1]); n_rows = the rows of d_v_corr that may be read, at least offsets[n_pairs] (the
+ * `capacity` given to gtsfm_compact_verified will do: the row count itself stays on the device; rows from n_rows on
+ * are never read); d_valid[n_pairs] (0 = skip the pair's rows; keep & isp_ok goes here) or NULL (all valid);
+ * d_kp_count[n_img] and kmax, the [n_img][kmax] keypoint layout of the verifier; d_kp_xy[n_img][kmax][2] or NULL.
+ * A node is (image i, keypoint k) with id i * kmax + k, so ascending id is ascending (i, k). n_img * kmax < 2^31 and
+ * n_rows < 2^31, else GTSFM_ERR_ARG.
+ * Semantics: a node is touched when a row of a valid pair names it; rows merge their two nodes transitively; every
+ * connected component of touched nodes is a candidate, and it is a track iff no two of its nodes share an image. A
+ * row whose two ends are one node gives a one-measurement track, as the Python reference does. A row of a valid pair
+ * whose image index is outside [0, n_img) or whose k >= min(d_kp_count[i], kmax) is ignored and counted.
+ * Canonical order (this library's definition; the reference's track order follows gtsam's internal representative
+ * and its SfmTrack2d.__eq__ ignores measurement order): tracks by ascending smallest node id, measurements inside a
+ * track by ascending node id, the order of gtsam's std::set<IndexPair> and the one test_dsf_tracks_estimator.py:86-112
+ * asserts. The outputs depend on the set of rows alone and are byte-identical from launch to launch.
+ * Outputs (caller-owned): d_track_offsets[track_cap + 1] (track t owns measurements offsets[t] .. offsets[t + 1]),
+ * d_track_img / d_track_kp[meas_cap], d_track_uv[meas_cap][2] = d_kp_xy of the node (written only when d_kp_xy and
+ * d_track_uv are both non-NULL), d_stats[5] = { n_tracks, n_measurements, n_components (the reference's len(key_set)),
+ * n_erroneous (components dropped for a repeated image), n_bad_rows }.
+ * Capacities: touched nodes <= min(2 * rows, n_img * kmax) bounds n_tracks and n_measurements, so that value always
+ * suffices for both. When a capacity is short nothing is written past it (measurement entries from meas_cap on and
+ * offsets entries after track_cap are dropped; the offsets that are written hold their true values) and d_stats still
+ * carries the true counts, as `capacity` does for gtsfm_compact_verified.
+ * Workspace: 30 bytes per node (n_img * kmax) plus the scans' tile sums; the query is constant in n_pairs and n_rows.
+ * n_pairs == 0 or n_rows == 0 returns GTSFM_OK with zeroed stats and offsets[0] = 0 and launches no kernel. A negative
+ * size, a NULL required pointer or a short workspace returns GTSFM_ERR_ARG. Nothing allocates or synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+/* 0 for an empty shape (a size <= 0) or an unsupported one (n_img * kmax or n_rows >= 2^31). */
+size_t gtsfm_tracks_workspace_bytes(int n_img, int kmax, int n_pairs, long long n_rows);
+
+int gtsfm_tracks_from_matches(const int* d_pairs, const int* d_offsets, const uint32_t* d_v_corr,
+                              const uint8_t* d_valid, int n_pairs, long long n_rows, const int* d_kp_count,
+                              const float* d_kp_xy, int n_img, int kmax, void* d_workspace, size_t workspace_bytes,
+                              int* d_track_offsets, long long track_cap, int* d_track_img, int* d_track_kp,
+                              float* d_track_uv, long long meas_cap, long long* d_stats, void* stream);
 
 #ifdef __cplusplus
 }
