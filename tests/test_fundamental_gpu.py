@@ -4,7 +4,8 @@ Known answer: the reference's TestRansacForFundamentalMatrix two-plane scene (te
 :22-30 over test_verifier_base.py:81-100): all 8 putatives verified, R and t within 2 deg.
 Oracle parity (oracle/fundamental.c): both compute the same double operations in the same order without FMA
 contraction, so F, the inlier mask, the inlier count and the hypothesis count are bit-identical; R/t come from the
-E-path decomposition (contracted on the GPU) and agree within 1e-9 per entry.
+recoverPose shared with the E path (twoview.hpp recover_pose, also compiled without contraction) and are checked
+within 1e-9 per entry.
 """
 import numpy as np
 import pytest

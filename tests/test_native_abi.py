@@ -38,6 +38,21 @@ def test_workspace_queries_without_gpu():
     assert lib.gtsfm_match_workspace_bytes(0, 2048, 128, 10, 1) == 0
 
 
+def test_verifier_workspace_sizes_pinned():
+    """The two verifiers' workspace sizes (ransac.hip RansacLayout, fundamental.hip FmatLayout) for two shapes, as
+    recorded before the layouts became structs: tools that read the workspace from Python rely on them."""
+    from gtsfm_amd import native
+
+    lib = native.lib()
+    assert lib.gtsfm_ransac_workspace_bytes(3, 100) == 2308352
+    assert lib.gtsfm_ransac_F_workspace_bytes(3, 100) == 14592
+    assert lib.gtsfm_ransac_workspace_bytes(619, 2048) == 538852096
+    assert lib.gtsfm_ransac_F_workspace_bytes(619, 2048) == 60850176
+    for fn in (lib.gtsfm_ransac_workspace_bytes, lib.gtsfm_ransac_F_workspace_bytes):
+        for n_pairs, mcap in ((0, 100), (-1, 100), (3, 0), (3, -1)):
+            assert fn(n_pairs, mcap) == 0
+
+
 def test_superpoint_weight_blob_layout():
     """The packed blob the Python side builds has exactly the size the library expects (include/gtsfm_hip.h)."""
     from gtsfm_amd import native
