@@ -1,9 +1,11 @@
 """2D tracks: the measurements of one scene point across images, with the reference's API
 (gtsfm/common/sfm_track.py:17-112), so that code written against the reference's SfmTrack2d reads these unchanged.
 """
-from typing import Iterable, List, NamedTuple
+from typing import Iterable, List, NamedTuple, Tuple
 
 import numpy as np
+
+from gtsfm_amd.common import geometry
 
 
 class SfmMeasurement(NamedTuple):
@@ -53,3 +55,40 @@ class SfmTrack2d(NamedTuple):
 
     def __ne__(self, other: object) -> bool:
         return not self.__eq__(other)
+
+
+if geometry.HAVE_GTSAM:  # pragma: no cover - exercised only where gtsam is installed
+    import gtsam  # type: ignore
+
+    SfmTrack = gtsam.SfmTrack
+else:
+
+    class SfmTrack:  # type: ignore[no-redef]
+        """Stand-in for gtsam.SfmTrack: a 3D point and its (camera index, uv) measurements, with the accessors the
+        reference's data association uses."""
+
+        def __init__(self, point3=(0.0, 0.0, 0.0)):
+            self._p = np.asarray(point3, dtype=np.float64).reshape(3).copy()
+            self._measurements: List[Tuple[int, np.ndarray]] = []
+
+        def point3(self) -> np.ndarray:
+            return self._p.copy()
+
+        def numberMeasurements(self) -> int:
+            return len(self._measurements)
+
+        def measurement(self, idx: int) -> Tuple[int, np.ndarray]:
+            return self._measurements[idx]
+
+        def addMeasurement(self, idx: int, uv) -> None:
+            self._measurements.append((int(idx), np.asarray(uv, dtype=np.float64).reshape(2).copy()))
+
+        def __reduce__(self):
+            return (_rebuild_sfm_track, (self._p, self._measurements))
+
+
+def _rebuild_sfm_track(point3, measurements):
+    track = SfmTrack(point3)
+    for i, uv in measurements:
+        track.addMeasurement(i, uv)
+    return track

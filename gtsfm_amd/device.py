@@ -660,3 +660,81 @@ def tracks_from_matches(pairs: torch.Tensor, offsets: torch.Tensor, v_corr: torc
                                      native.stream_handle(stream))
     native.check(rc, "gtsfm_tracks_from_matches")
     return t_off, t_img, t_kp, t_uv, stats
+
+
+class TriangulationResult:
+    """Per-track outputs of triangulate_tracks, all on the device: exit_code (T,) int32, point (T, 3) float64 (NaN
+    where the final triangulation did not succeed), avg_err (T,) float64, inlier (n_meas,) uint8, stats (8,) int64 in
+    the order of native.TRI_STATS_FIELDS, and, when asked for, n_hyp (T,) int32 and hyp_pair (hyp_cap,) int64."""
+
+    def __init__(self, exit_code, point, avg_err, inlier, stats, n_hyp=None, hyp_pair=None):
+        self.exit_code, self.point, self.avg_err, self.inlier, self.stats = exit_code, point, avg_err, inlier, stats
+        self.n_hyp, self.hyp_pair = n_hyp, hyp_pair
+
+
+def triangulate_tracks(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: torch.Tensor,
+                       wRc: torch.Tensor, wtc: torch.Tensor, intrinsics: torch.Tensor,
+                       cam_valid: Optional[torch.Tensor], mode: int, reproj_error_threshold: float,
+                       min_triangulation_angle: float = 0.0, n_hyp: int = 0, seed: int = 0,
+                       n_tracks: Optional[int] = None, n_tracks_dev: Optional[torch.Tensor] = None,
+                       track_id: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                       workspace: Optional[torch.Tensor] = None, workspace_bytes: Optional[int] = None,
+                       want_hypotheses: bool = False, hyp_cap: Optional[int] = None) -> TriangulationResult:
+    """Triangulates every track of a CSR (gtsfm_triangulate_tracks; semantics in include/gtsfm_hip.h).
+
+    track_offsets (>= T + 1,) int32, track_img (n_meas,) int32 and track_uv (n_meas, 2) float32 or float64: the
+    arrays tracks_from_matches returns (float32) or a host-built track (float64). n_tracks defaults to
+    track_offsets.numel() - 1; n_tracks_dev, an int64 device tensor whose first entry is the track count (the stats of
+    tracks_from_matches), makes n_tracks a capacity, so that the chain needs no host synchronisation. wRc (n_img, 3,
+    3), wtc (n_img, 3), intrinsics (n_img, 3) float64, cam_valid (n_img,) uint8 or None. mode is a
+    native.GTSFM_TRI_* value. workspace_bytes below the query's value forces more chunks (tests)."""
+    assert track_offsets.is_cuda and track_offsets.dtype == torch.int32 and track_offsets.is_contiguous()
+    assert track_img.is_cuda and track_img.dtype == torch.int32 and track_img.is_contiguous()
+    assert track_uv.is_cuda and track_uv.dtype in (torch.float32, torch.float64) and track_uv.is_contiguous()
+    n_meas = track_img.numel()
+    assert track_uv.numel() == 2 * n_meas
+    T = track_offsets.numel() - 1 if n_tracks is None else int(n_tracks)
+    assert 0 <= T < track_offsets.numel() or T == 0
+    for t in (wRc, wtc, intrinsics):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    n_img = intrinsics.numel() // 3
+    assert wRc.numel() == 9 * n_img and wtc.numel() == 3 * n_img and intrinsics.numel() == 3 * n_img
+    if cam_valid is not None:
+        assert cam_valid.is_cuda and cam_valid.dtype == torch.uint8 and cam_valid.is_contiguous()
+        assert cam_valid.numel() == n_img
+    if n_tracks_dev is not None:
+        assert n_tracks_dev.is_cuda and n_tracks_dev.dtype == torch.int64 and n_tracks_dev.numel() >= 1
+    if track_id is not None:
+        assert track_id.is_cuda and track_id.dtype == torch.int32 and track_id.is_contiguous()
+        assert track_id.numel() >= T
+    if mode == native.GTSFM_TRI_RANSAC_SAMPLE_BIASED_BASELINE:
+        raise NotImplementedError("RANSAC_SAMPLE_BIASED_BASELINE (a weighted draw without replacement) is not built")
+    n_hyp = min(int(n_hyp), 2 ** 31 - 1)
+    dev = track_offsets.device
+    exit_code = torch.empty(T, dtype=torch.int32, device=dev)
+    point = torch.full((T, 3), float("nan"), dtype=torch.float64, device=dev)
+    avg_err = torch.empty(T, dtype=torch.float64, device=dev)
+    inlier = torch.zeros(n_meas, dtype=torch.uint8, device=dev)
+    stats = torch.empty(8, dtype=torch.int64, device=dev)
+    t_n_hyp = hyp_pair = None
+    if want_hypotheses:
+        t_n_hyp = torch.zeros(T, dtype=torch.int32, device=dev)
+        hyp_cap = T * n_hyp if hyp_cap is None else int(hyp_cap)
+        hyp_pair = torch.full((max(hyp_cap, 1),), -1, dtype=torch.int64, device=dev)
+    L = native.lib()
+    need = L.gtsfm_triangulate_workspace_bytes(T, n_meas, n_hyp)
+    if workspace_bytes is not None:
+        need = int(workspace_bytes)
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_triangulate_tracks(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv),
+                                    1 if track_uv.dtype == torch.float64 else 0, _ptr(track_id), T,
+                                    _ptr(n_tracks_dev), n_meas, _ptr(wRc), _ptr(wtc), _ptr(intrinsics),
+                                    _ptr(cam_valid), n_img, int(mode), float(reproj_error_threshold),
+                                    float(min_triangulation_angle), n_hyp, int(seed) & (2 ** 64 - 1), _ptr(ws),
+                                    need if workspace_bytes is not None else ws.numel(), _ptr(exit_code), _ptr(point),
+                                    _ptr(avg_err), _ptr(inlier), _ptr(stats), _ptr(t_n_hyp), _ptr(hyp_pair),
+                                    0 if hyp_pair is None else hyp_cap, native.stream_handle(stream))
+    native.check(rc, "gtsfm_triangulate_tracks")
+    return TriangulationResult(exit_code, point, avg_err, inlier, stats, t_n_hyp, hyp_pair)

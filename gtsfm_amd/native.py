@@ -29,7 +29,7 @@ c_uint64 = ctypes.c_uint64
 c_longlong = ctypes.c_longlong
 
 # Mirrors include/gtsfm_hip.h
-ABI_VERSION = 404  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
+ABI_VERSION = 405  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
 GTSFM_OK = 0
 GTSFM_ERR_ARG = -1
 GTSFM_ERR_HIP = -2
@@ -52,6 +52,12 @@ BA2_STATUS_NOT_RUN = 3
 GTSFM_VG_MIN_EDGE_ERROR = 0
 GTSFM_VG_MEDIAN_EDGE_ERROR = 1
 VG_MAX_IMAGES = 8192  # gtsfm_viewgraph_cycle_filter's n_img ceiling
+GTSFM_TRI_NO_RANSAC = 0
+GTSFM_TRI_RANSAC_SAMPLE_UNIFORM = 1
+GTSFM_TRI_RANSAC_SAMPLE_BIASED_BASELINE = 2
+GTSFM_TRI_RANSAC_TOPK_BASELINES = 3
+TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
+                    "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
 # (name, restype, argtypes) of every symbol declared in include/gtsfm_hip.h
 SIGNATURES = {
@@ -138,6 +144,13 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p,
          c_size_t, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p],
+    ),
+    "gtsfm_triangulate_workspace_bytes": (c_size_t, [c_longlong, c_longlong, c_int]),
+    "gtsfm_triangulate_tracks": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_int, c_int, c_double, c_double, c_int, c_uint64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
     ),
 }
 

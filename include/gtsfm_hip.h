@@ -27,6 +27,10 @@
  *   gtsfm_tracks_*          <- gtsfm/data_association/dsf_tracks_estimator.py:56-85 DsfTracksEstimator.run,
  *                              cpp_dsf_tracks_estimator.py:63-74 (gtsam tracksFromPairwiseMatches) and
  *                              gtsfm/common/sfm_track.py:105-112 validate_unique_cameras
+ *   gtsfm_triangulate_*     <- gtsfm/data_association/point3d_initializer.py:117-380 Point3dInitializer.triangulate
+ *                              (execute_ransac_variant, sample_ransac_hypotheses, extract_measurements), one call per
+ *                              track from gtsfm/data_association/data_assoc.py:211-273 run_triangulation;
+ *                              gtsfm/utils/reprojection.py:48-83 and gtsfm/utils/tracks.py:82-102
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -48,7 +52,7 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
-#define GTSFM_HIP_ABI_VERSION 404
+#define GTSFM_HIP_ABI_VERSION 405
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
 const char* gtsfm_hip_target(void);
@@ -418,6 +422,77 @@ int gtsfm_tracks_from_matches(const int* d_pairs, const int* d_offsets, const ui
                               const float* d_kp_xy, int n_img, int kmax, void* d_workspace, size_t workspace_bytes,
                               int* d_track_offsets, long long track_cap, int* d_track_img, int* d_track_kp,
                               float* d_track_uv, long long meas_cap, long long* d_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Triangulation of 2D tracks to 3D landmarks: gtsfm/data_association/point3d_initializer.py:117-380
+ * Point3dInitializer.triangulate for every track of a CSR in one call (the reference makes one Python call per track,
+ * data_assoc.py:211-273, each with up to num_ransac_hypotheses gtsam.triangulatePoint3 calls).
+ *
+ * Tracks: d_track_offsets[n_tracks + 1] int32 and d_track_img[n_meas] int32 exactly as gtsfm_tracks_from_matches
+ * writes them; d_track_uv[n_meas][2] is that call's float32 track_uv (uv_is_f64 = 0) or a double array (uv_is_f64 = 1;
+ * SfmMeasurement.uv is float64). n_tracks is the number of tracks or, with d_n_tracks non-NULL, a capacity: the
+ * kernels then use min(n_tracks, d_n_tracks[0]) read on the device (pass the d_stats of gtsfm_tracks_from_matches: its
+ * entry 0 is the track count), so the chain needs no host synchronisation. n_meas bounds every offset; a track whose
+ * range is not inside [0, n_meas] gets exit code 2 and nothing else. d_track_id[n_tracks] (or NULL = the track's
+ * index) is the id the sampling hash is keyed by, so that a reordered set of tracks draws the same hypotheses.
+ * Cameras, indexed by image: d_wRc[n_img][9] row-major, d_wtc[n_img][3], d_intrinsics[n_img][3] = (f, u0, v0), all
+ * double, and d_cam_valid[n_img] (0 = the reference's camera missing from track_camera_dict or None) or NULL (all
+ * valid). An image index outside [0, n_img) counts as an invalid camera.
+ *
+ * Per-track semantics (point3d_initializer.py:225-295). err(measurement, X) is NaN for an invalid camera or z <= 0
+ * in the camera frame (projectSafe), else the pixel distance (reprojection.py:48-83); inlier iff err < threshold.
+ * triangulate(S) is gtsam.triangulatePoint3(rank_tol 1e-9, optimize): DLT null vector of the 2|S| x 4 system (folded
+ * row by row into a 4 x 4 triangular factor by Givens rotations, then one-sided Jacobi; rank >= 3), LM on the unit-noise
+ * reprojection factors (lambda 1, factor 10, <= 100 iterations, absoluteErrorTol 1), and it fails on rank < 3 or z <= 0
+ * in a camera of S.
+ * mode GTSFM_TRI_NO_RANSAC: best_inliers = all. Else the hypotheses are the pairs (k1 < k2) of the track's n
+ * measurements, pair index j in itertools.combinations order; m = min(n_hyp, n (n - 1) / 2) of them are evaluated: all
+ * of them when m equals their number, otherwise the m with the smallest (key_j, j), where
+ *   GTSFM_TRI_RANSAC_SAMPLE_UNIFORM: key_j = mix(mix(seed ^ mix(track id)) + j), mix = the splitmix64 finaliser
+ *       (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *       z ^ z >> 31) -- a fixed pseudo-random subset instead of the reference's np.random.choice(replace=False);
+ *   GTSFM_TRI_RANSAC_TOPK_BASELINES: key_j = ~bits(|wtc_i1 - wtc_i2|^2), the three fp64 products summed left to
+ *       right, so descending squared baseline (the reference's argsort of the norm, ties there unordered); a pair with
+ *       an invalid camera has key ~0;
+ *   GTSFM_TRI_RANSAC_SAMPLE_BIASED_BASELINE is not built: GTSFM_ERR_ARG.
+ * A hypothesis with an invalid camera or a failed two-view triangulate is skipped; else votes = inliers among all n
+ * measurements and avg_err their mean inlier error; votes == 0 does not compete. The winner is the minimum of
+ * (-votes, avg_err, j) (the reference keeps the first of equals in its random sample order); best_inliers is its
+ * inlier mask, all zero when nothing competes.
+ * Exit codes (TriangulationExitCode), in this order: < 2 inliers: 2; < 2 inliers with a valid camera: 3;
+ * triangulate(inliers with a valid camera) fails: 1; some inlier's err not < threshold (NaN included): 4;
+ * min_triangulation_angle > 0 and the largest angle (degrees) at the point between the rays to two inliers' camera
+ * centres is below it: 5; else 0.
+ * Outputs (caller-owned): d_exit_code[n_tracks] int32; d_point[n_tracks][3], written when the final triangulate
+ * succeeded (exits 0, 4, 5); d_avg_err[n_tracks] = nanmean of the inliers' errors for exits 0, 4, 5, NaN for 1-3;
+ * d_inlier[n_meas] = best_inliers, parallel to d_track_img; d_stats[8] int64 = the six exit-code counts, the inlier
+ * measurements of exit-0 tracks, the hypotheses evaluated (sum of m). Optional, for inspection: d_track_n_hyp[n_tracks]
+ * = m per track; d_hyp_pair[hyp_cap] = the pair index j of every evaluated hypothesis, track by track, ascending j
+ * inside a track (entries from hyp_cap on are dropped). Either may be NULL.
+ * All outputs are functions of a track's own measurements, cameras and id: they do not depend on the other tracks, on
+ * the workspace size or on the launch, and are byte-identical from call to call. No floating-point atomics.
+ * Workspace: 8 bytes per track plus a hypothesis buffer of 20 bytes per (track, hypothesis) item. The tracks are
+ * processed in chunks whose items fit the buffer; the query asks for all items up to 64 MiB, and at least one track's
+ * worst case min(n_hyp, n_meas (n_meas - 1) / 2) items. A smaller workspace that still holds that worst case gives
+ * more chunks and the same result; one that does not returns GTSFM_ERR_CAPACITY.
+ * n_tracks == 0 returns GTSFM_OK with zeroed stats. A negative size, a NULL required pointer, a threshold that is
+ * not > 0, n_hyp == 0 with a RANSAC mode or an unknown mode returns GTSFM_ERR_ARG. Nothing allocates or synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+#define GTSFM_TRI_NO_RANSAC 0
+#define GTSFM_TRI_RANSAC_SAMPLE_UNIFORM 1
+#define GTSFM_TRI_RANSAC_SAMPLE_BIASED_BASELINE 2
+#define GTSFM_TRI_RANSAC_TOPK_BASELINES 3
+/* 0 for an empty shape (n_tracks or n_meas <= 0), n_hyp < 0 or a size >= 2^31. */
+size_t gtsfm_triangulate_workspace_bytes(long long n_tracks, long long n_meas, int n_hyp);
+
+int gtsfm_triangulate_tracks(const int* d_track_offsets, const int* d_track_img, const void* d_track_uv, int uv_is_f64,
+                             const int* d_track_id, long long n_tracks, const long long* d_n_tracks, long long n_meas,
+                             const double* d_wRc, const double* d_wtc, const double* d_intrinsics,
+                             const uint8_t* d_cam_valid, int n_img, int mode, double reproj_error_threshold,
+                             double min_triangulation_angle, int n_hyp, uint64_t seed, void* d_workspace,
+                             size_t workspace_bytes, int* d_exit_code, double* d_point, double* d_avg_err,
+                             uint8_t* d_inlier, long long* d_stats, int* d_track_n_hyp, long long* d_hyp_pair,
+                             long long hyp_cap, void* stream);
 
 #ifdef __cplusplus
 }
