@@ -738,3 +738,75 @@ def triangulate_tracks(track_offsets: torch.Tensor, track_img: torch.Tensor, tra
                                     0 if hyp_pair is None else hyp_cap, native.stream_handle(stream))
     native.check(rc, "gtsfm_triangulate_tracks")
     return TriangulationResult(exit_code, point, avg_err, inlier, stats, t_n_hyp, hyp_pair)
+
+
+class GlobalBaResult:
+    """Outputs of global_ba, all on the device: wRc (n_img, 3, 3), wtc (n_img, 3), point (T, 3) float64, track_keep
+    (T,) and cam_keep (n_img,) uint8, stats (10,) float64 in the order of native.GBA_STATS_FIELDS."""
+
+    def __init__(self, wRc, wtc, point, track_keep, cam_keep, stats):
+        self.wRc, self.wtc, self.point = wRc, wtc, point
+        self.track_keep, self.cam_keep, self.stats = track_keep, cam_keep, stats
+
+
+def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: torch.Tensor, point: torch.Tensor,
+              track_valid: Optional[torch.Tensor], meas_valid: Optional[torch.Tensor], wRc: torch.Tensor,
+              wtc: torch.Tensor, intrinsics: torch.Tensor, cam_valid: Optional[torch.Tensor], robust: bool = False,
+              measurement_sigma: float = 1.0, cam_pose3_prior_sigma: float = 0.1, max_iterations: int = 0,
+              pcg_rel_tol: float = 1e-10, pcg_max_iter: int = 2000, reproj_error_thresh: float = float("inf"),
+              n_tracks: Optional[int] = None, n_tracks_dev: Optional[torch.Tensor] = None,
+              stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+              workspace_bytes: Optional[int] = None) -> GlobalBaResult:
+    """Bundle-adjusts every camera and landmark of a track CSR (gtsfm_global_ba; semantics in include/gtsfm_hip.h).
+
+    track_offsets / track_img / track_uv as for triangulate_tracks, point (T, 3) float64 its landmarks, track_valid
+    (T,) uint8 or bool or None, meas_valid (n_meas,) uint8 or None (the triangulation's inlier bytes). The call runs
+    its LM / PCG control flow on the host and synchronises the stream; only those control scalars reach the host.
+    workspace_bytes below the query's value is passed as is (tests of the capacity error)."""
+    assert track_offsets.is_cuda and track_offsets.dtype == torch.int32 and track_offsets.is_contiguous()
+    assert track_img.is_cuda and track_img.dtype == torch.int32 and track_img.is_contiguous()
+    assert track_uv.is_cuda and track_uv.dtype in (torch.float32, torch.float64) and track_uv.is_contiguous()
+    n_meas = track_img.numel()
+    assert track_uv.numel() == 2 * n_meas
+    T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
+    assert 0 <= T < track_offsets.numel() or T == 0
+    assert point.is_cuda and point.dtype == torch.float64 and point.is_contiguous() and point.numel() >= 3 * T
+    for t in (wRc, wtc, intrinsics):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    n_img = intrinsics.numel() // 3
+    assert wRc.numel() == 9 * n_img and wtc.numel() == 3 * n_img and intrinsics.numel() == 3 * n_img
+    if track_valid is not None:
+        if track_valid.dtype == torch.bool:
+            track_valid = track_valid.to(torch.uint8)
+        assert track_valid.is_cuda and track_valid.dtype == torch.uint8 and track_valid.is_contiguous()
+        assert track_valid.numel() >= T
+    for m, n in ((meas_valid, n_meas), (cam_valid, n_img)):
+        if m is not None:
+            assert m.is_cuda and m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == n
+    if n_tracks_dev is not None:
+        assert n_tracks_dev.is_cuda and n_tracks_dev.dtype == torch.int64 and n_tracks_dev.numel() >= 1
+    dev = track_offsets.device
+    wRc_out = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
+    wtc_out = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
+    point_out = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    track_keep = torch.empty(T, dtype=torch.uint8, device=dev)
+    cam_keep = torch.empty(n_img, dtype=torch.uint8, device=dev)
+    stats = torch.empty(10, dtype=torch.float64, device=dev)
+    L = native.lib()
+    need = L.gtsfm_global_ba_workspace_bytes(T, n_meas, n_img)
+    if T > 0 and n_meas > 0 and n_img > 0 and need == 0:
+        raise native.NativeError(f"gtsfm_global_ba: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_global_ba(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv),
+                           1 if track_uv.dtype == torch.float64 else 0, T, _ptr(n_tracks_dev), n_meas, _ptr(point),
+                           _ptr(track_valid), _ptr(meas_valid), _ptr(wRc), _ptr(wtc), _ptr(intrinsics),
+                           _ptr(cam_valid), n_img, 1 if robust else 0, float(measurement_sigma),
+                           float(cam_pose3_prior_sigma), int(max_iterations), float(pcg_rel_tol), int(pcg_max_iter),
+                           float(reproj_error_thresh), _ptr(ws),
+                           ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(wRc_out),
+                           _ptr(wtc_out), _ptr(point_out), _ptr(track_keep), _ptr(cam_keep), _ptr(stats),
+                           native.stream_handle(stream))
+    native.check(rc, "gtsfm_global_ba")
+    return GlobalBaResult(wRc_out, wtc_out, point_out, track_keep, cam_keep, stats)

@@ -29,7 +29,7 @@ c_uint64 = ctypes.c_uint64
 c_longlong = ctypes.c_longlong
 
 # Mirrors include/gtsfm_hip.h
-ABI_VERSION = 405  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
+ABI_VERSION = 406  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
 GTSFM_OK = 0
 GTSFM_ERR_ARG = -1
 GTSFM_ERR_HIP = -2
@@ -56,6 +56,10 @@ GTSFM_TRI_NO_RANSAC = 0
 GTSFM_TRI_RANSAC_SAMPLE_UNIFORM = 1
 GTSFM_TRI_RANSAC_SAMPLE_BIASED_BASELINE = 2
 GTSFM_TRI_RANSAC_TOPK_BASELINES = 3
+GBA_STATUS_OK = 0
+GBA_STATUS_NOTHING = 1  # no participating track or no modelled camera: the reference's early return
+GBA_STATS_FIELDS = ("initial_error", "final_error", "lm_iterations", "lm_trials", "pcg_iterations", "pcg_cap_hits",
+                    "cameras_modelled", "tracks_participating", "tracks_kept", "status")
 TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
                     "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
@@ -151,6 +155,13 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
          c_void_p, c_int, c_int, c_double, c_double, c_int, c_uint64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p],
+    ),
+    "gtsfm_global_ba_workspace_bytes": (c_size_t, [c_longlong, c_longlong, c_int]),
+    "gtsfm_global_ba": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_double, c_int, c_double, c_void_p,
+         c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
 }
 

@@ -4,7 +4,8 @@
  * Every entry point takes plain pointers and sizes. Pointers named d_* are DEVICE pointers (HBM);
  * `stream` is a hipStream_t passed as void* (NULL = default stream). No entry point allocates,
  * synchronises or copies to the host: callers own every buffer and size workspaces with the
- * matching *_workspace_bytes() query, so a call can be captured into a hipGraph.
+ * matching *_workspace_bytes() query, so a call can be captured into a hipGraph. The one exception is
+ * gtsfm_global_ba, whose LM / PCG control flow reads scalars back and synchronises its stream (see its block).
  * Return value: GTSFM_OK (0) or a negative GTSFM_ERR_* code. Degenerate DATA (too few matches,
  * no model) is never an error: it is reported per pair, as the reference reports a failure tuple.
  *
@@ -31,6 +32,8 @@
  *                              (execute_ransac_variant, sample_ransac_hypotheses, extract_measurements), one call per
  *                              track from gtsfm/data_association/data_assoc.py:211-273 run_triangulation;
  *                              gtsfm/utils/reprojection.py:48-83 and gtsfm/utils/tracks.py:82-102
+ *   gtsfm_global_ba*        <- gtsfm/bundle/bundle_adjustment.py:58-397 BundleAdjustmentOptimizer.run_ba,
+ *                              gtsfm/bundle/global_ba.py and gtsfm/common/gtsfm_data.py:389-427 filter_landmarks
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -52,7 +55,7 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
-#define GTSFM_HIP_ABI_VERSION 405
+#define GTSFM_HIP_ABI_VERSION 406
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
 const char* gtsfm_hip_target(void);
@@ -493,6 +496,76 @@ int gtsfm_triangulate_tracks(const int* d_track_offsets, const int* d_track_img,
                              size_t workspace_bytes, int* d_exit_code, double* d_point, double* d_avg_err,
                              uint8_t* d_inlier, long long* d_stats, int* d_track_n_hyp, long long* d_hyp_pair,
                              long long hyp_cap, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Global bundle adjustment: gtsfm/bundle/bundle_adjustment.py:58-397 BundleAdjustmentOptimizer
+ * (run_ba_stage_with_filtering :292-357, the factor graph :106-267, run_ba :359-397), gtsfm/bundle/global_ba.py and
+ * gtsfm/common/gtsfm_data.py:389-427 filter_landmarks: one GTSAM LevenbergMarquardtOptimizer over every camera pose and
+ * every landmark, the consumer of gtsfm_triangulate_tracks' device tensors.
+ *
+ * Inputs, laid out as the two upstream calls write them: the track CSR d_track_offsets[n_tracks + 1], d_track_img[n_meas],
+ * d_track_uv[n_meas][2] (float32, or double with uv_is_f64 = 1); n_tracks is the track count or, with d_n_tracks
+ * non-NULL, a capacity (min(n_tracks, d_n_tracks[0]) is used, read on the device); d_point[n_tracks][3] the initial
+ * landmarks; d_track_valid[n_tracks], a byte per track (the `valid` of DataAssociation.run_triangulation_arrays) or NULL
+ * (all); d_meas_valid[n_meas] (the triangulation's inlier bytes) or NULL (all): a measurement with 0 is not a factor and
+ * is not checked by the filter, as the reference's SfmTrack holds inliers only. Cameras indexed by image: d_wRc[n_img][9]
+ * row-major, d_wtc[n_img][3], d_intrinsics[n_img][3] = (f, u0, v0), d_cam_valid[n_img] or NULL (all valid); an image
+ * index outside [0, n_img) counts as an invalid camera.
+ * Options: robust (Huber 1.345 on the whitened residual norm), measurement_sigma (pixels), cam_pose3_prior_sigma (the
+ * reference's default 0.1), max_iterations (0 = GTSAM's 100), pcg_rel_tol (1e-10 is the binding's default),
+ * pcg_max_iter (2000), reproj_error_thresh (+inf = the reference's None).
+ *
+ * The problem. A measurement is usable when its d_meas_valid byte is set and its camera is valid. A track participates
+ * when it is valid, its offsets lie inside [0, n_meas] and at least two of its measurements are usable. A camera is
+ * modelled when it is valid and has a usable measurement in a participating track. Variables: one Pose3 per modelled
+ * camera, one point per participating track. Factors: a reprojection factor per usable measurement of a participating
+ * track; PriorFactorPose3 on the modelled camera of lowest index at its initial pose, isotropic
+ * cam_pose3_prior_sigma; PriorFactorPoint3, sigma 0.1, on the first participating track at its initial point.
+ * Calibration is held fixed at k1 = k2 = 0, the approximation gtsfm_ba2_batched states (the limit of the reference's
+ * 1e-5 calibration prior), so shared_calib has no effect. BetweenFactorPose3 relative-pose priors are not built.
+ * Taken from gtsfm_ba2_batched (ba2.hip), generalised from camera 0 = identity to an arbitrary first camera: the
+ * reprojection residual and its Jacobians (pose in the body frame, rotation first), the Huber loss and sqrt-weight
+ * scaling of the rows, a measurement with z <= 0 contributing nothing to the linear system or the cost, the pose prior
+ * as Logmap(X0^-1 X) with an identity Jacobian, the point prior, the Pose3 retraction (full exponential map) and the
+ * point update p + dp.
+ * The optimiser is GTSAM's LM as ba2.hip restates it: lambda 1e-5, factor 10, upper bound 1e5, isotropic damping,
+ * minModelFidelity 1e-3, relative and absolute error tolerances 1e-5. Each trial eliminates the points (3 x 3 blocks,
+ * damped) and solves the 6C x 6C reduced camera system without forming it, by preconditioned conjugate gradients from
+ * a zero start; the preconditioner is the inverse of the 6 x 6 diagonal blocks of the damped Schur complement. PCG
+ * stops at ||r||_2 <= pcg_rel_tol ||b||_2 or after pcg_max_iter products (a cap hit is counted; the step then goes
+ * through the ordinary accept test). Then the points are back-substituted and the linearised and non-linear costs of
+ * the step evaluated. Every sum is taken in a fixed order and there are no floating-point atomics: two calls on the
+ * same inputs return byte-identical outputs.
+ *
+ * Outputs (caller-owned): d_wRc_out[n_img][9], d_wtc_out[n_img][3] (a camera that is not modelled is copied through);
+ * d_point_out[n_tracks][3] (non-participating tracks copied through); d_track_keep[n_tracks] bytes, GtsfmData.
+ * filter_landmarks: 1 iff the track participates and every measurement whose d_meas_valid byte is set has a valid
+ * camera (the reference's error is NaN otherwise), lies in front of it and reprojects with error <
+ * reproj_error_thresh; with an infinite threshold every participating track is kept, without the cheirality test
+ * (bundle_adjustment.py:353-355); d_cam_keep[n_img] bytes: the camera has such a measurement in a kept track (the
+ * cameras of filtered_result); d_stats[10] doubles = { initial error, final error (graph.error), LM iterations, LM
+ * trials, PCG iterations in total, PCG cap hits, cameras modelled, tracks participating, tracks kept, status }.
+ * Status 0: optimised. Status 1: nothing to optimise (no participating track or no modelled camera, the reference's
+ * early return at :319-324): inputs copied through, both keep masks zero, errors and counts 0.
+ * The LM and PCG control flow runs on the host: the call enqueues its kernels on `stream` and reads a few scalars back
+ * per PCG iteration and per LM trial, so, unlike every other entry point, it SYNCHRONISES its stream (and returns with
+ * the stream idle) and cannot be captured into a hipGraph. It still allocates nothing: all state lives in the
+ * workspace, 160 bytes per measurement for the linearisation plus about 350 bytes per track and 1 KiB per camera.
+ * A negative size, a size >= 2^31 - 1, n_img > 2^20, a NULL required pointer, a sigma, tolerance or threshold that is
+ * not > 0, max_iterations < 0 or pcg_max_iter <= 0 returns GTSFM_ERR_ARG; a workspace smaller than the query's answer
+ * returns GTSFM_ERR_CAPACITY. n_tracks, n_meas or n_img == 0 gives status 1.
+ * ---------------------------------------------------------------------------------------------- */
+/* 0 for an empty shape (a size <= 0) or an unsupported one (n_tracks or n_meas >= 2^31 - 1, n_img > 2^20). */
+size_t gtsfm_global_ba_workspace_bytes(long long n_tracks, long long n_meas, int n_img);
+
+int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const void* d_track_uv, int uv_is_f64,
+                    long long n_tracks, const long long* d_n_tracks, long long n_meas, const double* d_point,
+                    const uint8_t* d_track_valid, const uint8_t* d_meas_valid, const double* d_wRc,
+                    const double* d_wtc, const double* d_intrinsics, const uint8_t* d_cam_valid, int n_img, int robust,
+                    double measurement_sigma, double cam_pose3_prior_sigma, int max_iterations, double pcg_rel_tol,
+                    int pcg_max_iter, double reproj_error_thresh, void* d_workspace, size_t workspace_bytes,
+                    double* d_wRc_out, double* d_wtc_out, double* d_point_out, uint8_t* d_track_keep,
+                    uint8_t* d_cam_keep, double* d_stats, void* stream);
 
 #ifdef __cplusplus
 }
