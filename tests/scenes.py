@@ -85,3 +85,32 @@ def random_two_view(rng, n_in: int, n_out: int, noise_px: float = 0.5, f: float 
     inl = np.zeros(len(kp1), bool)
     inl[: len(uv1)] = True
     return kp1[perm], kp2[perm], K, R, t, inl[perm]
+
+
+def random_two_view_k(rng, n_in: int, n_out: int, K1, K2, noise_px: float = 0.5, w=1920, h=1080):
+    """random_two_view with one calibration per view: K1, K2 = (f, u0, v0) of view 1 / view 2. Returns pixel coords of
+    both views, R, unit t (X2 = R X1 + t) and the inlier flags. (Its own draw order; random_two_view's is untouched.)"""
+    (f1, u1, v1), (f2, u2, v2) = K1, K2
+    ang = rng.normal(size=3)
+    ang = ang / np.linalg.norm(ang) * np.radians(rng.uniform(5, 25))
+    th = np.linalg.norm(ang)
+    k = ang / th
+    R = np.eye(3) + np.sin(th) * skew(k) + (1 - np.cos(th)) * skew(k) @ skew(k)
+    t = rng.normal(size=3)
+    t = t / np.linalg.norm(t)
+    X = np.stack([rng.uniform(-4, 4, n_in), rng.uniform(-3, 3, n_in), rng.uniform(6, 15, n_in)], 1)
+    X2 = X @ R.T + t
+    ok = X2[:, 2] > 0.5
+    X, X2 = X[ok], X2[ok]
+    uv1 = X[:, :2] / X[:, 2:] * f1 + np.array([u1, v1])
+    uv2 = X2[:, :2] / X2[:, 2:] * f2 + np.array([u2, v2])
+    uv1 += rng.normal(scale=noise_px, size=uv1.shape)
+    uv2 += rng.normal(scale=noise_px, size=uv2.shape)
+    o1 = np.stack([rng.uniform(0, w, n_out), rng.uniform(0, h, n_out)], 1)
+    o2 = np.stack([rng.uniform(0, w, n_out), rng.uniform(0, h, n_out)], 1)
+    kp1 = np.vstack([uv1, o1])
+    kp2 = np.vstack([uv2, o2])
+    perm = rng.permutation(len(kp1))
+    inl = np.zeros(len(kp1), bool)
+    inl[: len(uv1)] = True
+    return kp1[perm], kp2[perm], R, t, inl[perm]

@@ -29,11 +29,14 @@ def dev():
     return torch.device("cuda")
 
 
-def _compact_ref(idx, cnt, mask, status, n_inl, min_inl, min_ratio):
+def _compact_ref(idx, cnt, mask, status, n_inl, min_inl, min_ratio, ratio_inliers=None):
+    """ratio_inliers: the counts the inlier ratio is taken on (the pre-BA ones after BA); rows, offsets and the
+    min-inlier guard stay on n_inl."""
     rows, off, ok = [], [0], []
     for p in range(len(cnt)):
         M, st, n = int(cnt[p]), int(status[p]), int(n_inl[p])
-        ratio = n / M if (st == 0 and M > 0) else 0.0
+        nr = n if ratio_inliers is None else int(ratio_inliers[p])
+        ratio = nr / M if (st == 0 and M > 0) else 0.0
         ok.append(int(st == 0 and not (ratio < min_ratio or (0 < n < min_inl))))
         r = idx[p, :M][mask[p, :M].astype(bool)] if st == 0 else np.zeros((0, 2), np.int32)
         rows.append(r)
@@ -41,7 +44,9 @@ def _compact_ref(idx, cnt, mask, status, n_inl, min_inl, min_ratio):
     return np.array(off), np.concatenate(rows) if rows else np.zeros((0, 2)), np.array(ok)
 
 
-@pytest.mark.parametrize("P,mcap", [(1, 7), (37, 130), (300, 64), (1000, 513)])
+# P = 1024, 1025 and 2500: the scan's threads take one pair each with none idle, two each with half of them idle, and
+# three each with a ragged last thread
+@pytest.mark.parametrize("P,mcap", [(1, 7), (37, 130), (300, 64), (1000, 513), (1024, 9), (1025, 9), (2500, 70)])
 def test_compact_verified_matches_restatement(dev, P, mcap):
     from gtsfm_amd import device
 
@@ -71,6 +76,104 @@ def test_compact_verified_matches_restatement(dev, P, mcap):
     np.testing.assert_array_equal(off.cpu().numpy(), e_off)
     np.testing.assert_array_equal(rows.cpu().numpy()[: e_off[-1]], e_rows.reshape(-1, 2))
     np.testing.assert_array_equal(ok.cpu().numpy()[:P], e_ok)
+
+
+class _Res:
+    """The verifier outputs gtsfm_compact_verified consumes."""
+
+    def __init__(self, dev, mask, status, n_inl):
+        self.mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
+        self.status = torch.from_numpy(np.ascontiguousarray(status, np.int32)).to(dev)
+        self.n_inliers = torch.from_numpy(np.ascontiguousarray(n_inl, np.int32)).to(dev)
+
+
+def _random_compact_case(rng, P, mcap):
+    idx = rng.integers(0, 5000, size=(P, mcap, 2)).astype(np.int32)
+    cnt = rng.integers(0, mcap + 1, size=P).astype(np.int32)
+    mask = (rng.random((P, mcap)) < rng.random((P, 1))).astype(np.uint8)
+    mask[np.arange(mcap)[None, :] >= cnt[:, None]] = 1  # junk past the putatives is ignored
+    n_inl = np.array([int(mask[p, : cnt[p]].sum()) for p in range(P)], np.int32)
+    status = rng.choice([0, 0, 0, 1, 2], size=P).astype(np.int32)
+    status[cnt < 6] = 1
+    n_inl[status != 0] = 0
+    return idx, cnt, mask, status, n_inl
+
+
+def test_compact_ratio_inliers_decide_the_ratio_only(dev):
+    """d_ratio_inliers (the pre-BA counts): isp_ok follows ratio_inliers / M, offsets and rows follow n_inliers."""
+    from gtsfm_amd import device
+
+    rng = np.random.default_rng(77)
+    P, mcap = 200, 200
+    idx, cnt, mask, status, n_inl = _random_compact_case(rng, P, mcap)
+    ratio_inl = rng.integers(0, cnt + 1).astype(np.int32)  # unrelated to n_inl, within [0, M]
+    ratio_inl[status != 0] = 0
+    e_off, e_rows, e_ok = _compact_ref(idx, cnt, mask, status, n_inl, 15, 0.3, ratio_inliers=ratio_inl)
+    _, _, plain_ok = _compact_ref(idx, cnt, mask, status, n_inl, 15, 0.3)
+    assert np.count_nonzero(ratio_inl != n_inl) > P // 2
+    assert np.count_nonzero((e_ok == 1) & (plain_ok == 0)) >= 3 and np.count_nonzero((e_ok == 0) & (plain_ok == 1)) >= 3
+    off, rows, ok = device.compact_verified(torch.from_numpy(idx).to(dev), torch.from_numpy(cnt).to(dev),
+                                            _Res(dev, mask, status, n_inl), 15, 0.3, int(cnt.sum()),
+                                            ratio_inliers=torch.from_numpy(ratio_inl).to(dev))
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(off.cpu().numpy(), e_off)
+    np.testing.assert_array_equal(rows.cpu().numpy()[: e_off[-1]], e_rows.reshape(-1, 2))
+    np.testing.assert_array_equal(ok.cpu().numpy()[:P], e_ok)
+
+
+@pytest.mark.parametrize("min_ratio", [0.1, 0.0])
+def test_compact_inlier_support_boundaries(dev, min_ratio):
+    """inlier_support_processor.py:73-87 on its boundaries, min_inliers = 5: failure iff ratio < min_ratio or
+    0 < n < min_inliers, so a ratio exactly at min_ratio and a count exactly at min_inliers pass."""
+    from gtsfm_amd import device
+
+    #        (n, M): 5/50 = ratio 0.1 exactly and n == min_inliers; 4/40 = 0.1 but n == min_inliers - 1; 5/20 and
+    #        4/20 the same two counts well above the ratio; 0/30 no inliers with status 0; 5/51 just below 0.1
+    cases = [(5, 50), (4, 40), (5, 20), (4, 20), (0, 30), (5, 51)]
+    expect = {0.1: [1, 0, 1, 0, 0, 0], 0.0: [1, 0, 1, 0, 1, 1]}[min_ratio]
+    P, mcap = len(cases), 64
+    rng = np.random.default_rng(5)
+    idx = rng.integers(0, 5000, size=(P, mcap, 2)).astype(np.int32)
+    cnt = np.array([M for _, M in cases], np.int32)
+    n_inl = np.array([n for n, _ in cases], np.int32)
+    mask = np.zeros((P, mcap), np.uint8)
+    for p, (n, M) in enumerate(cases):
+        mask[p, rng.choice(M, n, replace=False)] = 1
+    status = np.zeros(P, np.int32)
+    e_off, e_rows, e_ok = _compact_ref(idx, cnt, mask, status, n_inl, 5, min_ratio)
+    assert e_ok.tolist() == expect
+    off, rows, ok = device.compact_verified(torch.from_numpy(idx).to(dev), torch.from_numpy(cnt).to(dev),
+                                            _Res(dev, mask, status, n_inl), 5, min_ratio, int(n_inl.sum()))
+    torch.cuda.synchronize()
+    assert ok.cpu().numpy()[:P].tolist() == expect
+    np.testing.assert_array_equal(off.cpu().numpy(), e_off)
+    np.testing.assert_array_equal(rows.cpu().numpy()[: e_off[-1]], e_rows.reshape(-1, 2))
+
+
+def test_compact_capacity_below_the_total(dev):
+    """A v_corr buffer shorter than the total: offsets are still the full scan, every pair that fits has its rows,
+    and nothing at or past `capacity` rows is written."""
+    from gtsfm_amd import device
+
+    rng = np.random.default_rng(78)
+    P, mcap = 60, 40
+    idx, cnt, mask, status, n_inl = _random_compact_case(rng, P, mcap)
+    e_off, e_rows, e_ok = _compact_ref(idx, cnt, mask, status, n_inl, 15, 0.1)
+    total = int(e_off[-1])
+    capacity = total // 2
+    fits = [p for p in range(P) if status[p] == 0 and e_off[p] + n_inl[p] <= capacity]
+    assert 0 < len(fits) and any(status[p] == 0 and n_inl[p] > 0 and e_off[p] + n_inl[p] > capacity for p in range(P))
+    big = torch.full((total + 16, 2), -7, dtype=torch.int32, device=dev)
+    off, rows, ok = device.compact_verified(torch.from_numpy(idx).to(dev), torch.from_numpy(cnt).to(dev),
+                                            _Res(dev, mask, status, n_inl), 15, 0.1, capacity,
+                                            out_v_corr=big[:capacity])
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(off.cpu().numpy(), e_off)
+    np.testing.assert_array_equal(ok.cpu().numpy()[:P], e_ok)
+    got = big.cpu().numpy()
+    for p in fits:
+        np.testing.assert_array_equal(got[e_off[p]: e_off[p + 1]], e_rows.reshape(-1, 2)[e_off[p]: e_off[p + 1]])
+    assert (got[capacity:] == -7).all()
 
 
 def _engine(kernels, device, n_img, scene, world=1, rank=0):

@@ -126,3 +126,84 @@ def test_F_batch_equals_single_pair_calls(dev):
         single = v.verify(kps[i1], kps[i2], m, cals[i1], cals[i2])
         assert np.array_equal(batch[(i1, i2)][2], single[2])
         assert np.array_equal(geometry.rotation_matrix(batch[(i1, i2)][0]), geometry.rotation_matrix(single[0]))
+
+
+# ---- edges: putative counts on the LMedS / wave boundaries, max_iters off the batch size, degenerate pairs ----------
+# Inputs from tests/twoview_batch.py (tests/test_twoview_inputs.py pins what the oracle does on them). Columns of the
+# mask at or past match_count[p] are not compared: the header does not define them.
+
+def _run_F(dev, pairs_xy, **kw):
+    from gtsfm_amd import device
+    from tests import twoview_batch as tb
+
+    kp, intr, pairs, mi, cnt = tb.pack_private(pairs_xy)
+    res = device.ransac_fundamental(torch.from_numpy(kp).to(dev), torch.from_numpy(intr).to(dev),
+                                    torch.from_numpy(pairs).to(dev), torch.from_numpy(mi).to(dev),
+                                    torch.from_numpy(cnt).to(dev), 4.0, **kw)
+    return {k: getattr(res, k).cpu().numpy() for k in ("status", "n_inliers", "n_hyp", "F", "mask")}
+
+
+def _assert_F_pair_equals_oracle(g, p, ref, M):
+    """Pair p of a launch against oracle.ransac_F's result for it (None = no model)."""
+    from gtsfm_amd import native
+
+    if ref is None:
+        assert g["status"][p] == native.RANSAC_STATUS_NO_MODEL, (p, g["status"][p])
+        assert g["n_inliers"][p] == 0 and not g["mask"][p, :M].any(), p
+        return
+    rF, rmask, rn, rnh = ref
+    assert g["status"][p] == native.RANSAC_STATUS_OK, (p, g["status"][p])
+    assert np.array_equal(g["F"][p], rF), (p, g["F"][p], rF)
+    assert np.array_equal(g["mask"][p, :M], rmask), p
+    assert g["n_inliers"][p] == rn and g["n_hyp"][p] == rnh, (p, g["n_inliers"][p], rn, g["n_hyp"][p], rnh)
+
+
+def test_F_putative_counts_on_the_boundaries(dev, oracle_mod):
+    """M = 7, 8, 14 (LMedS, noisy, two gross outliers), 15, 16 (first RANSAC sizes), 63, 64, 65, 128, 129 (wave
+    boundaries), one launch."""
+    from gtsfm_amd import native
+    from tests import twoview_batch as tb
+
+    pairs_xy = tb.f_edge_pairs()
+    assert tuple(len(a) for a, _ in pairs_xy) == tb.F_EDGE_COUNTS
+    g = _run_F(dev, pairs_xy, max_iters=200000)
+    n_ok = 0
+    for p, (a, b) in enumerate(pairs_xy):
+        M = len(a)
+        if M == 7:
+            assert g["status"][p] == native.RANSAC_STATUS_TOO_FEW
+            assert g["n_inliers"][p] == 0 and g["n_hyp"][p] == 0 and not g["mask"][p, :M].any()
+            continue
+        ref = oracle_mod.ransac_F(a, b, 4.0, max_iters=200000, pair_id=p)
+        _assert_F_pair_equals_oracle(g, p, ref, M)
+        n_ok += ref is not None
+        if M >= 15:
+            assert ref is not None, M
+    assert n_ok >= 8
+
+
+@pytest.mark.parametrize("max_iters", [1, 64, 65, 100])
+def test_F_max_iters_off_the_batch_size(dev, oracle_mod, max_iters):
+    from tests import twoview_batch as tb
+
+    a, b = tb.f_max_iters_pair()
+    g = _run_F(dev, [(a, b)], max_iters=max_iters)
+    ref = oracle_mod.ransac_F(a, b, 4.0, max_iters=max_iters, pair_id=0)
+    assert ref is not None
+    _assert_F_pair_equals_oracle(g, 0, ref, len(a))
+    assert g["n_hyp"][0] == ref[3] and g["n_hyp"][0] % 64 == 0 and g["n_hyp"][0] >= max_iters
+
+
+def test_F_degenerate_pairs_give_no_model(dev, oracle_mod):
+    """All putatives on a line in image 1, and all at one point in both images: status NO_MODEL, no inliers, an
+    all-zero mask (the oracle does not report its hypothesis count without a model, so none is compared); the ordinary
+    pairs before, between and after them in the launch still equal the oracle."""
+    from tests import twoview_batch as tb
+
+    line, point = tb.f_degenerate_pairs()
+    pairs_xy = [tb.f_ordinary_pair(1), line, tb.f_ordinary_pair(2), point, tb.f_ordinary_pair(3)]
+    g = _run_F(dev, pairs_xy, max_iters=200000)
+    for p, (a, b) in enumerate(pairs_xy):
+        ref = oracle_mod.ransac_F(a, b, 4.0, max_iters=200000, pair_id=p)
+        assert (ref is None) == (p in (1, 3)), p
+        _assert_F_pair_equals_oracle(g, p, ref, len(a))
