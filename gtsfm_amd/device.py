@@ -810,3 +810,150 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
                            native.stream_handle(stream))
     native.check(rc, "gtsfm_global_ba")
     return GlobalBaResult(wRc_out, wtc_out, point_out, track_keep, cam_keep, stats)
+
+
+class TransAvgMeasurements:
+    """Outputs of transavg_measurements, all on the device: key (n_edges + n_meas, 2) int32, dir (.., 3) float64, valid
+    (..,) uint8, selected (n_tracks,) int32, cam_valid (n_img,) uint8, counts (4,) int64 = valid camera edges, track
+    slots in use, selected tracks, track measurements in a camera without rotation."""
+
+    def __init__(self, key, dir, valid, selected, cam_valid, counts, n_edges):
+        self.key, self.dir, self.valid, self.selected = key, dir, valid, selected
+        self.cam_valid, self.counts, self.n_edges = cam_valid, counts, n_edges
+
+
+def transavg_measurements(edges: torch.Tensor, i2Ui1: torch.Tensor, edge_valid: Optional[torch.Tensor],
+                          wRi: torch.Tensor, rot_valid: Optional[torch.Tensor],
+                          track_offsets: Optional[torch.Tensor] = None, track_img: Optional[torch.Tensor] = None,
+                          track_uv: Optional[torch.Tensor] = None, intrinsics: Optional[torch.Tensor] = None,
+                          measurements_per_camera: int = 12, n_tracks: Optional[int] = None,
+                          n_tracks_dev: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                          workspace: Optional[torch.Tensor] = None) -> TransAvgMeasurements:
+    """World-frame direction measurements and track selection of 1DSfM (gtsfm_transavg_measurements; semantics in
+    include/gtsfm_hip.h). edges (E, 2) int32 = (i1, i2), i2Ui1 (E, 3) float64, wRi (n_img, 3, 3) float64, the valid
+    masks uint8 or None; the track CSR as tracks_from_matches returns it (or None: camera edges only)."""
+    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous() and edges.dim() == 2
+    E = edges.shape[0]
+    assert edges.shape[1] == 2 and E > 0
+    for t in (i2Ui1, wRi):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    n_img = wRi.numel() // 9
+    assert i2Ui1.numel() == 3 * E and wRi.numel() == 9 * n_img and n_img > 0
+    for m, n in ((edge_valid, E), (rot_valid, n_img)):
+        if m is not None:
+            assert m.is_cuda and m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == n
+    dev = edges.device
+    T = n_meas = 0
+    if track_offsets is not None:
+        assert track_offsets.is_cuda and track_offsets.dtype == torch.int32 and track_offsets.is_contiguous()
+        assert track_img.is_cuda and track_img.dtype == torch.int32 and track_img.is_contiguous()
+        assert track_uv.is_cuda and track_uv.dtype in (torch.float32, torch.float64) and track_uv.is_contiguous()
+        assert intrinsics.is_cuda and intrinsics.dtype == torch.float64 and intrinsics.is_contiguous()
+        assert intrinsics.numel() == 3 * n_img
+        n_meas = track_img.numel()
+        assert track_uv.numel() == 2 * n_meas
+        T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
+        assert 0 <= T < track_offsets.numel() or T == 0
+    if n_tracks_dev is not None:
+        assert n_tracks_dev.is_cuda and n_tracks_dev.dtype == torch.int64 and n_tracks_dev.numel() >= 1
+    key = torch.empty((E + n_meas, 2), dtype=torch.int32, device=dev)
+    dirs = torch.empty((E + n_meas, 3), dtype=torch.float64, device=dev)
+    valid = torch.empty(E + n_meas, dtype=torch.uint8, device=dev)
+    selected = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    cam_valid = torch.empty(n_img, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    L = native.lib()
+    need = L.gtsfm_transavg_measurements_workspace_bytes(E, T, n_meas, n_img)
+    if need == 0:
+        raise native.NativeError(f"gtsfm_transavg_measurements: unsupported shape {E} edges, {T} tracks, {n_img} images")
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_transavg_measurements(_ptr(edges), _ptr(i2Ui1), _ptr(edge_valid), E, _ptr(wRi), _ptr(rot_valid), n_img,
+                                       _ptr(track_offsets), _ptr(track_img), _ptr(track_uv),
+                                       1 if track_uv is not None and track_uv.dtype == torch.float64 else 0, T,
+                                       _ptr(n_tracks_dev), n_meas, _ptr(intrinsics), int(measurements_per_camera),
+                                       _ptr(ws), ws.numel(), _ptr(key), _ptr(dirs), _ptr(valid), _ptr(selected),
+                                       _ptr(cam_valid), _ptr(counts), native.stream_handle(stream))
+    native.check(rc, "gtsfm_transavg_measurements")
+    return TransAvgMeasurements(key, dirs, valid, selected[:T], cam_valid, counts, E)
+
+
+def transavg_mfas(key: torch.Tensor, dirs: torch.Tensor, valid: Optional[torch.Tensor], n_nodes: int,
+                  proj: torch.Tensor, threshold: float = 0.125, want_violated: bool = False,
+                  stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                  ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """MFAS outlier weights over every projection direction in one launch (gtsfm_transavg_mfas). key (n, 2) int32,
+    dirs (n, 3) float64, valid (n,) uint8 or None, proj (n_dir, 3) float64. Returns (outlier_sum (n,) float64, inlier
+    (n,) uint8, violated (n_dir, ceil(n / 32)) int32 holding the uint32 bit words, or None)."""
+    assert key.is_cuda and key.dtype == torch.int32 and key.is_contiguous() and key.dim() == 2 and key.shape[1] == 2
+    n = key.shape[0]
+    assert dirs.is_cuda and dirs.dtype == torch.float64 and dirs.is_contiguous() and dirs.numel() == 3 * n
+    assert proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.dim() == 2
+    n_dir = proj.shape[0]
+    if valid is not None:
+        assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == n
+    if n_nodes > native.TA_MFAS_MAX_NODES:
+        raise native.NativeError(f"gtsfm_transavg_mfas holds its node state in LDS: {n_nodes} nodes exceed "
+                                 f"{native.TA_MFAS_MAX_NODES}")
+    dev = key.device
+    osum = torch.empty(n, dtype=torch.float64, device=dev)
+    inlier = torch.empty(n, dtype=torch.uint8, device=dev)
+    viol = torch.empty((n_dir, (n + 31) // 32), dtype=torch.int32, device=dev) if want_violated else None
+    L = native.lib()
+    need = L.gtsfm_transavg_mfas_workspace_bytes(n, int(n_nodes), n_dir)
+    if need == 0:
+        raise native.NativeError(f"gtsfm_transavg_mfas: unsupported shape {n} measurements, {n_nodes} nodes, {n_dir} "
+                                 "directions")
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_transavg_mfas(_ptr(key), _ptr(dirs), _ptr(valid), n, int(n_nodes), _ptr(proj), n_dir, float(threshold),
+                               _ptr(ws), ws.numel(), _ptr(osum), _ptr(inlier), _ptr(viol), native.stream_handle(stream))
+    native.check(rc, "gtsfm_transavg_mfas")
+    return osum, inlier, viol
+
+
+class TransAvgResult:
+    """Outputs of transavg_recover, all on the device: wti (n_img, 3) float64, wti_valid (n_img,) uint8, landmark
+    (n_landmarks, 3), landmark_valid, stats (10,) float64 in the order of native.TA_STATS_FIELDS."""
+
+    def __init__(self, wti, wti_valid, landmark, landmark_valid, stats):
+        self.wti, self.wti_valid, self.landmark, self.landmark_valid, self.stats = (wti, wti_valid, landmark,
+                                                                                    landmark_valid, stats)
+
+
+def transavg_recover(key: torch.Tensor, dirs: torch.Tensor, inlier: torch.Tensor, n_img: int, n_landmarks: int,
+                     rot_valid: Optional[torch.Tensor] = None, robust: bool = True, scale: float = 1.0, seed: int = 0,
+                     max_iterations: int = 0, pcg_rel_tol: float = 1e-10, pcg_max_iter: int = 2000,
+                     stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                     ) -> TransAvgResult:
+    """Camera and landmark positions from the inlier direction measurements (gtsfm_transavg_recover). Runs its LM / PCG
+    control flow on the host and synchronises the stream."""
+    assert key.is_cuda and key.dtype == torch.int32 and key.is_contiguous() and key.dim() == 2 and key.shape[1] == 2
+    n = key.shape[0]
+    assert dirs.is_cuda and dirs.dtype == torch.float64 and dirs.is_contiguous() and dirs.numel() == 3 * n
+    assert inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == n
+    if rot_valid is not None:
+        assert rot_valid.is_cuda and rot_valid.dtype == torch.uint8 and rot_valid.numel() == n_img
+    dev = key.device
+    wti = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
+    wti_valid = torch.empty(n_img, dtype=torch.uint8, device=dev)
+    land = torch.empty((n_landmarks, 3), dtype=torch.float64, device=dev)
+    land_valid = torch.empty(n_landmarks, dtype=torch.uint8, device=dev)
+    stats = torch.empty(10, dtype=torch.float64, device=dev)
+    L = native.lib()
+    need = L.gtsfm_transavg_recover_workspace_bytes(n, int(n_img), int(n_landmarks))
+    if need == 0:
+        raise native.NativeError(f"gtsfm_transavg_recover: unsupported shape {n} measurements, {n_img} images, "
+                                 f"{n_landmarks} landmarks")
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_transavg_recover(_ptr(key), _ptr(dirs), _ptr(inlier), n, int(n_img), int(n_landmarks), _ptr(rot_valid),
+                                  1 if robust else 0, float(scale), int(seed) & (2 ** 64 - 1), int(max_iterations),
+                                  float(pcg_rel_tol), int(pcg_max_iter), _ptr(ws), ws.numel(), _ptr(wti),
+                                  _ptr(wti_valid), _ptr(land) if n_landmarks else None,
+                                  _ptr(land_valid) if n_landmarks else None, _ptr(stats), native.stream_handle(stream))
+    native.check(rc, "gtsfm_transavg_recover")
+    return TransAvgResult(wti, wti_valid, land, land_valid, stats)

@@ -29,7 +29,7 @@ c_uint64 = ctypes.c_uint64
 c_longlong = ctypes.c_longlong
 
 # Mirrors include/gtsfm_hip.h
-ABI_VERSION = 406  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
+ABI_VERSION = 407  # GTSFM_HIP_ABI_VERSION: lib() refuses a library built for another ABI
 GTSFM_OK = 0
 GTSFM_ERR_ARG = -1
 GTSFM_ERR_HIP = -2
@@ -60,6 +60,12 @@ GBA_STATUS_OK = 0
 GBA_STATUS_NOTHING = 1  # no participating track or no modelled camera: the reference's early return
 GBA_STATS_FIELDS = ("initial_error", "final_error", "lm_iterations", "lm_trials", "pcg_iterations", "pcg_cap_hits",
                     "cameras_modelled", "tracks_participating", "tracks_kept", "status")
+TA_STATUS_OK = 0
+TA_STATUS_NOTHING = 1  # no measurement kept
+TA_STATUS_NOT_FINITE = 2
+TA_MFAS_MAX_NODES = 8000  # GTSFM_TRANSAVG_MFAS_MAX_NODES
+TA_STATS_FIELDS = ("initial_error", "final_error", "lm_iterations", "lm_trials", "pcg_iterations", "pcg_cap_hits",
+                   "sets_optimised", "factors", "cameras_valid", "status")
 TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
                     "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
@@ -162,6 +168,25 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_double, c_int, c_double, c_void_p,
          c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_transavg_measurements_workspace_bytes": (c_size_t, [c_int, c_longlong, c_longlong, c_int]),
+    "gtsfm_transavg_measurements": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+         c_longlong, c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_transavg_mfas_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
+    "gtsfm_transavg_mfas": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_int, c_double, c_void_p, c_size_t, c_void_p,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_transavg_recover_workspace_bytes": (c_size_t, [c_longlong, c_int, c_int]),
+    "gtsfm_transavg_recover": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_double, c_uint64, c_int, c_double,
+         c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
 }
 

@@ -55,7 +55,7 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
-#define GTSFM_HIP_ABI_VERSION 406
+#define GTSFM_HIP_ABI_VERSION 407
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
 const char* gtsfm_hip_target(void);
@@ -566,6 +566,115 @@ int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const vo
                     int pcg_max_iter, double reproj_error_thresh, void* d_workspace, size_t workspace_bytes,
                     double* d_wRc_out, double* d_wtc_out, double* d_point_out, uint8_t* d_track_keep,
                     uint8_t* d_cam_keep, double* d_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Translation averaging, 1DSfM: gtsfm/averaging/translation/averaging_1dsfm.py TranslationAveraging1DSFM, in three
+ * calls that share one measurement list. The global rotations wRi are an input (rotation averaging is not built).
+ *
+ * The measurement list. Nodes: camera i is node i, landmark s (the s-th selected track) is node n_img + s. Measurement
+ * e has d_meas_key[e] = (key1, key2) int32, a unit direction d_meas_dir[e][3] double and a byte d_meas_valid[e].
+ * gtsfm_transavg_measurements writes n_edges + n_meas slots: slot e < n_edges is camera edge e (keys (i2, i1), the
+ * flip of _binary_measurements_from_dict :152-153); the track measurements follow from slot n_edges on, selected track
+ * by selected track in selection order, a track's measurements in CSR order (keys (camera, n_img + s), :154-155).
+ * Unused slots have valid = 0, keys -1 and a zero direction. d_counts[4] int64 = { valid camera edges, track slots in
+ * use, selected tracks, track measurements whose camera has no rotation }.
+ *
+ * gtsfm_transavg_measurements: (a) get_valid_measurements_in_world_frame :593-616 and _get_landmark_directions
+ * :341-372, (b) _select_tracks_for_averaging :273-339.
+ * (a) Edge e = d_edges[e] = (i1, i2) with d_i2Ui1[e][3] is valid iff d_edge_valid[e] != 0 (NULL = all), both indices
+ * lie in [0, n_img), i1 != i2 and d_rot_valid[i2] != 0 (NULL = all). Its direction is Unit3(wRi[i2] i2Ui1): the
+ * row-major 3 x 3 product, each row summed left to right, then every component divided by the norm sqrt(x x + y y +
+ * z z); a zero vector stays zero. Both endpoints become valid cameras (d_cam_valid[n_img]). A track measurement (u, v)
+ * in camera c has direction Unit3(wRi[c] Unit3(((u - u0) / f, (v - v0) / f, 1))), calibration (f, u0, v0) =
+ * d_intrinsics[c], k1 = k2 = 0. Where the reference raises (camera c valid but d_rot_valid[c] == 0) the slot stays
+ * unused and counts[3] is incremented.
+ * (b) Integer only, so exact: a track (d_track_offsets / d_track_img / d_track_uv as gtsfm_triangulate_tracks takes
+ * them, n_tracks a capacity when d_n_tracks is given) is restricted to its measurements in valid cameras and dropped
+ * when fewer than 3 remain. improvement[t] starts at that count, remaining[c] at measurements_per_camera (the
+ * reference's TRACKS_MEASUREMENTS_PER_CAMERA = 12). Repeat: take the track of largest improvement, lowest index first
+ * (np.argmax); stop when it is <= 0; append it to d_selected; set its improvement to 0; for each of its measurements
+ * in order whose camera c has remaining[c] > 0: decrement remaining[c], and when that reaches 0 lower the improvement
+ * of every track by one, not below 0, once per measurement that the track has in c (the reference's camera -> tracks
+ * lookup holds one entry per measurement). d_selected[n_tracks] holds the track ids in selection order, -1 after them.
+ * One workgroup runs the loop; nothing synchronises and nothing allocates.
+ *
+ * gtsfm_transavg_mfas: (c) the MFAS outlier weights of compute_inliers :212-237, all projection directions in one
+ * launch (the reference: one gtsam.MFAS per direction in a Python loop, "TODO: parallelize this step").
+ * d_proj[n_dir][3] are the projection directions. Only measurements with valid != 0 (NULL = all), keys in [0, n_nodes)
+ * and key1 != key2 take part. For direction d, w_e = u_e . d with the three products summed x, y, z left to right;
+ * edge e is oriented key1 -> key2 if w_e >= 0, else key2 -> key1, with weight |w_e|. inSum[v] and outSum[v] add the
+ * weights of v's incoming and outgoing edges in ascending measurement index. Then, until no node remains: if a
+ * remaining node has inSum < 1e-8, pick the one of lowest index; otherwise pick the remaining node with the largest
+ * (outSum + 1) / (inSum + 1), lowest index on ties. Remove it; each remaining out-neighbour gets inSum -= |w| and each
+ * remaining in-neighbour outSum -= |w|, one subtraction per removed edge (two edges to the same neighbour: ascending
+ * measurement index), so a node's sequence of subtractions is fixed by the removal order alone. Edge e is violated for
+ * d when its sink was removed before its source; its outlier weight is then |w_e|, else 0.
+ * d_outlier_sum[e] adds the outlier weights in ascending direction index; d_inlier[e] = 1 iff the measurement takes
+ * part and outlier_sum / n_dir < outlier_weight_threshold (the reference's 0.125). d_violated (optional, else NULL):
+ * [n_dir][ceil(n_meas / 32)] uint32, bit (e & 31) of word e >> 5 set iff e is violated for that direction.
+ * Stated deviation: GTSAM's MFAS walks an unordered_map, so its choice among simultaneous sources and among exact ties
+ * of the heuristic is implementation-defined; the lowest-index rule replaces it.
+ * One workgroup per direction keeps inSum, outSum and the removal position in LDS, 20 bytes per node, so n_nodes <=
+ * GTSFM_TRANSAVG_MFAS_MAX_NODES (160 KiB of LDS); beyond it, for n_dir > 2^20 or n_meas >= 2^30: GTSFM_ERR_ARG.
+ * The loop runs n_nodes steps by construction; there is no wait between workgroups, no floating-point atomic, nothing
+ * allocates or synchronises, and two calls return the same bytes.
+ *
+ * gtsfm_transavg_recover: (d) the last loop of compute_inliers :239-256 and __run_averaging :374-430, i.e. GTSAM's
+ * TranslationRecovery.run(measurements, scale) without priors.
+ * A measurement is kept iff d_meas_inlier[e] != 0, key1 is a camera, key2 a node, key1 != key2 and, for a track
+ * measurement (key2 >= n_img), its camera is an endpoint of an inlier camera edge. Every node of a kept measurement
+ * is a variable. Nodes joined by a kept measurement with a zero direction (every |component| <= 1e-9) share one
+ * position, that of the lowest index of their set (TranslationRecovery's same-translation sets); measurements inside
+ * a set are dropped. Factors, per remaining measurement (a, b) = the sets of (key1, key2): residual
+ * normalize(t_b - t_a) - u_e, isotropic sigma 0.01, under Huber k = 1.345 on the whitened norm when robust != 0, with
+ * the sqrt-weight row scaling of gtsfm_global_ba. Gauge: PriorFactor<Point3> at the origin, sigma 0.01, on key1 of the
+ * first remaining measurement in input order. Scale: BetweenFactor<Point3>(key1, key2, scale u) on that measurement
+ * with its noise model. Initial values (stated deviation: GTSAM draws uniform (-1, 1) from a static mt19937(42) in
+ * hash-map order): coordinate k of node v is 2 U - 1, U = (h >> 11) 2^-53, h = mix(mix(seed ^ mix(v)) + k), mix the
+ * splitmix64 finaliser stated at gtsfm_triangulate_tracks. A set with no factor sits at the origin (GTSAM does that
+ * only when no factor remains at all).
+ * LM: GTSAM's default LevenbergMarquardtParams as gtsfm_global_ba restates them (lambda 1e-5, factor 10, upper bound
+ * 1e5, minModelFidelity 1e-3, relative and absolute tolerances 1e-5, max_iterations 0 = 100). Linear solve: conjugate
+ * gradients on the damped normal equations, never formed (one pass over the factors, one over the node-major lists),
+ * preconditioned by the inverse 3 x 3 diagonal blocks, from a zero start, until ||r|| <= pcg_rel_tol ||b|| or
+ * pcg_max_iter products (counted as a cap hit). No elimination.
+ * Outputs: d_wti[n_img][3] and d_wti_valid[n_img] (0: the camera is not a variable or d_rot_valid is 0; position
+ * zeroed), d_landmark[n_landmarks][3] and d_landmark_valid, d_stats[10] doubles = { initial error, final error, LM
+ * iterations, LM trials, PCG iterations, PCG cap hits, optimised sets, factors (without prior and scale), valid
+ * cameras, status }. Status 0: done (possibly with no factor: every variable at the origin); 1: no measurement kept;
+ * 2: the error is not finite. As gtsfm_global_ba, the LM / PCG control flow is host code, so the call SYNCHRONISES its
+ * stream; it allocates nothing, sums in a fixed order, uses no floating-point atomic, and two calls return the same
+ * bytes. n_meas <= 0 or >= 2^30, n_img <= 0, n_img + n_landmarks > 2^24, a NULL required pointer, max_iterations < 0,
+ * pcg_rel_tol not > 0 or pcg_max_iter <= 0: GTSFM_ERR_ARG; a short workspace: GTSFM_ERR_CAPACITY.
+ * ---------------------------------------------------------------------------------------------- */
+#define GTSFM_TRANSAVG_MFAS_MAX_NODES 8000
+/* 0 for n_edges <= 0, n_img <= 0 or an unsupported shape (a size >= 2^30, n_img > 2^20). */
+size_t gtsfm_transavg_measurements_workspace_bytes(int n_edges, long long n_tracks, long long n_meas, int n_img);
+
+int gtsfm_transavg_measurements(const int* d_edges, const double* d_i2Ui1, const uint8_t* d_edge_valid, int n_edges,
+                                const double* d_wRi, const uint8_t* d_rot_valid, int n_img,
+                                const int* d_track_offsets, const int* d_track_img, const void* d_track_uv,
+                                int uv_is_f64, long long n_tracks, const long long* d_n_tracks, long long n_meas,
+                                const double* d_intrinsics, int measurements_per_camera, void* d_workspace,
+                                size_t workspace_bytes, int* d_meas_key, double* d_meas_dir, uint8_t* d_meas_valid,
+                                int* d_selected, uint8_t* d_cam_valid, long long* d_counts, void* stream);
+
+/* 0 for an empty or unsupported shape (see above). */
+size_t gtsfm_transavg_mfas_workspace_bytes(long long n_meas, int n_nodes, int n_dir);
+
+int gtsfm_transavg_mfas(const int* d_meas_key, const double* d_meas_dir, const uint8_t* d_meas_valid, long long n_meas,
+                        int n_nodes, const double* d_proj, int n_dir, double outlier_weight_threshold,
+                        void* d_workspace, size_t workspace_bytes, double* d_outlier_sum, uint8_t* d_inlier,
+                        uint32_t* d_violated, void* stream);
+
+/* 0 for an empty or unsupported shape (see above). */
+size_t gtsfm_transavg_recover_workspace_bytes(long long n_meas, int n_img, int n_landmarks);
+
+int gtsfm_transavg_recover(const int* d_meas_key, const double* d_meas_dir, const uint8_t* d_meas_inlier,
+                           long long n_meas, int n_img, int n_landmarks, const uint8_t* d_rot_valid, int robust,
+                           double scale, uint64_t seed, int max_iterations, double pcg_rel_tol, int pcg_max_iter,
+                           void* d_workspace, size_t workspace_bytes, double* d_wti, uint8_t* d_wti_valid,
+                           double* d_landmark, uint8_t* d_landmark_valid, double* d_stats, void* stream);
 
 #ifdef __cplusplus
 }
