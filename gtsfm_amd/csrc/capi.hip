@@ -12,7 +12,8 @@ extern "C" {
 // 4.03: gtsfm_viewgraph_* added (cycle-consistent rotation view-graph filter)
 // 4.04: gtsfm_tracks_* added (2D feature tracks from verified correspondences, union-find)
 // 4.05: gtsfm_triangulate_* added; 4.06: gtsfm_global_ba added
-// 4.07: gtsfm_transavg_* added (1DSfM translation averaging: measurements, MFAS, recovery)
+// 4.07: gtsfm_transavg_* added (1DSfM translation averaging: measurements, MFAS, recovery); gtsfm_rotavg_* added
+//       (Shonan rotation averaging) without a new number: symbols only
 int gtsfm_hip_abi_version(void) { return GTSFM_HIP_ABI_VERSION; }
 
 const char* gtsfm_hip_target(void) { return "gfx950"; }

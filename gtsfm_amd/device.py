@@ -957,3 +957,54 @@ def transavg_recover(key: torch.Tensor, dirs: torch.Tensor, inlier: torch.Tensor
                                   _ptr(land_valid) if n_landmarks else None, _ptr(stats), native.stream_handle(stream))
     native.check(rc, "gtsfm_transavg_recover")
     return TransAvgResult(wti, wti_valid, land, land_valid, stats)
+
+
+class RotAvgResult:
+    """Outputs of rotavg_shonan, all on the device: wRi (n_img, 3, 3) float64 (zero where invalid), rot_valid (n_img,)
+    uint8, stats (12,) float64 in the order of native.RA_STATS_FIELDS."""
+
+    def __init__(self, wRi, rot_valid, stats):
+        self.wRi, self.rot_valid, self.stats = wRi, rot_valid, stats
+
+
+def rotavg_shonan(edges: torch.Tensor, aRb: torch.Tensor, kappa: Optional[torch.Tensor], edge_valid: Optional[torch.Tensor],
+                  n_img: int, wRi_init: Optional[torch.Tensor] = None, seed: int = 0, p_min: int = 5, p_max: int = 30,
+                  optimality_threshold: float = -1e-4, grad_rel_tol: float = 1e-10, max_iterations: int = 100,
+                  pcg_rel_tol: float = 1e-2, pcg_max_iter: int = 200, eig_tol: float = 1e-8, eig_max_steps: int = 4000,
+                  stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                  ) -> RotAvgResult:
+    """Global rotations from relative ones by Shonan averaging with an optimality certificate (gtsfm_rotavg_shonan).
+    edges (E, 2) int32 = (a, b) with aRb (E, 3, 3) float64 asking wRa aRb = wRb; kappa (E,) float64 or None (= 1).
+    Runs its LM / PCG / Lanczos control flow on the host and synchronises the stream."""
+    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous() and edges.dim() == 2 and \
+        edges.shape[1] == 2
+    n = edges.shape[0]
+    assert aRb.is_cuda and aRb.dtype == torch.float64 and aRb.is_contiguous() and aRb.numel() == 9 * n
+    if kappa is not None:
+        assert kappa.is_cuda and kappa.dtype == torch.float64 and kappa.is_contiguous() and kappa.numel() == n
+    if edge_valid is not None:
+        assert edge_valid.is_cuda and edge_valid.dtype == torch.uint8 and edge_valid.is_contiguous() and \
+            edge_valid.numel() == n
+    if wRi_init is not None:
+        assert wRi_init.is_cuda and wRi_init.dtype == torch.float64 and wRi_init.is_contiguous() and \
+            wRi_init.numel() == 9 * n_img
+    dev = edges.device
+    wRi = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
+    rot_valid = torch.empty(n_img, dtype=torch.uint8, device=dev)
+    stats = torch.empty(12, dtype=torch.float64, device=dev)
+    L = native.lib()
+    need = L.gtsfm_rotavg_workspace_bytes(n, int(n_img), int(p_max))
+    if workspace is None:
+        if need == 0:
+            raise native.NativeError(f"gtsfm_rotavg_shonan: unsupported shape {n} edges, {n_img} images, p_max {p_max}")
+        workspace = _workspace(need, dev)
+    ws = workspace
+    if stream is not None:
+        ws.record_stream(stream)
+    rc = L.gtsfm_rotavg_shonan(_ptr(edges), _ptr(aRb), _ptr(kappa), _ptr(edge_valid), n, int(n_img), _ptr(wRi_init),
+                               int(seed) & (2 ** 64 - 1), int(p_min), int(p_max), float(optimality_threshold),
+                               float(grad_rel_tol), int(max_iterations), float(pcg_rel_tol), int(pcg_max_iter),
+                               float(eig_tol), int(eig_max_steps), _ptr(ws), ws.numel(), _ptr(wRi), _ptr(rot_valid),
+                               _ptr(stats), native.stream_handle(stream))
+    native.check(rc, "gtsfm_rotavg_shonan")
+    return RotAvgResult(wRi, rot_valid, stats)

@@ -66,6 +66,12 @@ TA_STATUS_NOT_FINITE = 2
 TA_MFAS_MAX_NODES = 8000  # GTSFM_TRANSAVG_MFAS_MAX_NODES
 TA_STATS_FIELDS = ("initial_error", "final_error", "lm_iterations", "lm_trials", "pcg_iterations", "pcg_cap_hits",
                    "sets_optimised", "factors", "cameras_valid", "status")
+RA_STATUS_CERTIFIED = 0
+RA_STATUS_NOTHING = 1  # no valid edge
+RA_STATUS_UNCERTIFIED = 2  # p_max reached without a certificate; the rotations are still returned
+RA_STATUS_NOT_FINITE = 3
+RA_STATS_FIELDS = ("initial_cost", "final_cost", "final_p", "min_eigenvalue", "eigen_residual", "lm_iterations",
+                   "pcg_iterations", "pcg_cap_hits", "lanczos_steps", "cameras_valid", "edges_used", "status")
 TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
                     "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
@@ -187,6 +193,12 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_double, c_uint64, c_int, c_double,
          c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_rotavg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gtsfm_rotavg_shonan": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_uint64, c_int, c_int, c_double, c_double,
+         c_int, c_double, c_int, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
 }
 

@@ -55,6 +55,8 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
+/* Stays 407 with gtsfm_rotavg_* added: new symbols only, no existing signature or meaning changed, so no caller of
+ * a 407 library breaks. */
 #define GTSFM_HIP_ABI_VERSION 407
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
@@ -569,7 +571,7 @@ int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const vo
 
 /* ----------------------------------------------------------------------------------------------
  * Translation averaging, 1DSfM: gtsfm/averaging/translation/averaging_1dsfm.py TranslationAveraging1DSFM, in three
- * calls that share one measurement list. The global rotations wRi are an input (rotation averaging is not built).
+ * calls that share one measurement list. The global rotations wRi are an input (gtsfm_rotavg_shonan below computes them).
  *
  * The measurement list. Nodes: camera i is node i, landmark s (the s-th selected track) is node n_img + s. Measurement
  * e has d_meas_key[e] = (key1, key2) int32, a unit direction d_meas_dir[e][3] double and a byte d_meas_valid[e].
@@ -675,6 +677,82 @@ int gtsfm_transavg_recover(const int* d_meas_key, const double* d_meas_dir, cons
                            double scale, uint64_t seed, int max_iterations, double pcg_rel_tol, int pcg_max_iter,
                            void* d_workspace, size_t workspace_bytes, double* d_wti, uint8_t* d_wti_valid,
                            double* d_landmark, uint8_t* d_landmark_valid, double* d_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Rotation averaging, Shonan: gtsfm/averaging/rotation/shonan.py ShonanRotationAveraging, i.e. GTSAM's
+ * ShonanAveraging3::run(initial, p_min, p_max) with LevenbergMarquardtParams::CeresDefaults (:54), no Huber (:56)
+ * and certifyOptimality (:57), in one call. "GTSAM does" below is GTSAM 4.2 as remembered; this text is the contract.
+ *
+ * The problem. Edge e = (a, b) = d_edges[e] with aRb = d_aRb[e] (row-major 3 x 3) and kappa = d_kappa[e] (NULL = 1)
+ * asks that wRa aRb = wRb. A two-view measurement (i1, i2) -> i2Ri1 is the edge a = i2, b = i1, aRb = i2Ri1
+ * (BetweenFactorPose3(i2_, i1_, i2Ti1) :75); a pose prior on (i1, i2) with value i1Ti2 is a = i1, b = i2, aRb =
+ * R(i1Ti2) (:97); kappa = 1 / sigma^2 with sigma = two_view_rotation_sigma (:65) or sqrt(mean(diag(covariance)))
+ * (:85-90). A pair given twice contributes twice. At level p camera i has Y_i in St(p, 3), a p x 3 matrix with
+ * orthonormal columns, stored [n][p][3]; the cost is f(Y) = sum_e kappa_e |Y_a aRb - Y_b|_F^2 = tr(Y Q Y'), Q the
+ * 3n x 3n connection Laplacian. Stated deviation: GTSAM optimises over SO(p) and uses the first three columns, the
+ * same problem with a redundant gauge.
+ *
+ * Setup. An edge is valid iff d_edge_valid[e] != 0 (NULL = all), both indices lie in [0, n_img), a != b, aRb is
+ * finite and kappa is finite and > 0. Of the connected components of the valid edges the largest is kept, ties to the
+ * one holding the lowest camera index (stated deviation: GTSAM requires a connected graph and GTSfM prunes to the
+ * largest component upstream). Cameras outside it and cameras with no valid edge (the reference's None, :195-197) get
+ * d_rot_valid = 0 and a zero matrix. The kept cameras are renumbered consecutively in ascending index
+ * (old_to_new_idxes :183-184) and the half-edges listed node-major in ascending edge index.
+ *
+ * The staircase, p = p_min .. p_max with 3 <= p_min <= p_max <= 30 (the reference: 5 and 30, :50-51).
+ * Initial values: rows 0..2 of Y_i are d_wRi_init[i] (row-major), the other rows zero; with d_wRi_init NULL the
+ * seeded rotation of camera i: entry k of a 3 x 3 matrix is 2 U - 1, U = (h >> 11) 2^-53, h = mix(mix(seed ^ mix(i))
+ * + k), mix the splitmix64 finaliser stated at gtsfm_triangulate_tracks, then its polar factor, third column negated
+ * when the determinant is negative (stated deviation: GTSAM's initializeRandomly uses its own generator). Either way
+ * Y_i then goes through the retraction once.
+ * Level p: Riemannian Levenberg-Marquardt on St(p, 3)^n. Gradient g = 2 Proj_Y(Y Q), Proj_Y(V)_i = V_i - Y_i
+ * sym(Y_i' V_i); Hessian H V = 2 Proj_Y(V Q - V Lambda), Lambda_i = sym(Y_i' (Y Q)_i); damped system (H + lambda D)
+ * x = -g with D_i = 2 sum of the kappa at camera i, the diagonal of 2 Q (CeresDefaults' diagonalDamping; stated
+ * deviation: the diagonal of Q, not of the projected Hessian). CeresDefaults: lambdaInitial 1e-4, lambdaFactor 2,
+ * lambdaUpperBound 1e32, lambdaLowerBound 1e-16, useFixedLambdaFactor false, minModelFidelity 1e-3: a step is
+ * accepted when rho = (f - f_new) / (-<g, x> - <x, H x> / 2) > 1e-3 and f_new < f, then lambda *= max(1/3, 1 -
+ * (2 rho - 1)^3), not below 1e-16, and the factor returns to 2; otherwise lambda *= factor, factor *= 2, and the
+ * level ends when lambda passes 1e32. Stated deviation: CeresDefaults stops on relativeErrorTol 1e-6 after at most
+ * 50 iterations; here a level stops when |g| <= grad_rel_tol G0, G0 = sqrt(3 sum_i D_i^2) (the norm of 2 diag(Q) Y),
+ * or after max_iterations accepted steps.
+ * Linear solve: conjugate gradients, matrix-free, preconditioned by the inverse diagonal blocks of 2 (1 + lambda) Q,
+ * D_i (1 + lambda) I, from a zero start until |r| <= pcg_rel_tol |g| or pcg_max_iter products (a cap hit); when a
+ * product finds <p, (H + lambda D) p> <= 0 the solve stops with what it has, the preconditioned steepest descent
+ * step if it was the first product.
+ * Retraction: the polar factor A (A'A)^-1/2 of A = Y_i + x_i (3 x 3 Jacobi).
+ * Certificate: S = Q - blockdiag(Lambda). Its smallest eigenpair (theta, v) by Lanczos with the basis on the device,
+ * full reorthogonalisation (two passes), the tridiagonal problem solved on the host by cyclic Jacobi, cycles of at
+ * most 128 vectors restarted from the Ritz vector, a seeded start vector, until |S v - theta v| <= eig_tol or
+ * eig_max_steps products. theta is the Rayleigh quotient of the normalised Ritz vector, so theta >= lambda_min(S).
+ * The level is certified iff theta > optimality_threshold (the reference's -1e-4): "not certified" is therefore always
+ * right, "certified" relies on the residual, which is reported in d_stats and enters the decision only as the
+ * stopping rule (when the step cap ends the iteration the last theta decides).
+ * Not certified and p < p_max: append a zero row to every Y_i and step along e_{p+1} v_i' through the retraction, from
+ * alpha = max(10.24, 0.1 / |theta|), halving while alpha >= 0.01; the first point of lower cost is taken, else the
+ * last tried (GTSAM's initializeWithDescent, without its gradient-norm condition). p_max reached uncertified: the
+ * reference raises; here status 2 and the rotations are rounded from the last level and returned.
+ * Rounding (roundSolution): the three dominant eigenvectors U (p x 3) of sum_i Y_i Y_i' (host Jacobi) give the blocks
+ * U' Y_i; when more than half of them have a negative determinant the third row of every block is negated; each block
+ * is projected to the closest rotation by a 3 x 3 SVD. No anchoring: the frame is what rounding gives.
+ *
+ * Outputs: d_wRi[n_img][9] row-major, d_rot_valid[n_img], d_stats[12] doubles = { initial cost, final cost, final p,
+ * theta, eigen residual, accepted LM steps, PCG products, PCG cap hits, Lanczos products, valid cameras, edges used,
+ * status }. Status 0: certified; 1: no valid edge; 2: p_max reached uncertified; 3: a cost was not finite (no camera
+ * valid). The LM / PCG / Lanczos control flow is host code, so the call SYNCHRONISES its stream; it allocates
+ * nothing, sums in a fixed order (a camera's half-edges are split over the lanes of one wave and added in a fixed
+ * tree), uses no floating-point atomic, and two calls return the same bytes.
+ * n_edges <= 0 or >= 2^30, n_img <= 0 or > 2^20, p_min < 3, p_max < p_min, p_max > 30, a NULL d_edges, d_aRb,
+ * d_workspace or output, a tolerance not > 0, a cap <= 0 or a non-finite threshold: GTSFM_ERR_ARG; a short workspace:
+ * GTSFM_ERR_CAPACITY.
+ * ---------------------------------------------------------------------------------------------- */
+/* 0 for an empty or unsupported shape (see above). */
+size_t gtsfm_rotavg_workspace_bytes(int n_edges, int n_img, int p_max);
+
+int gtsfm_rotavg_shonan(const int* d_edges, const double* d_aRb, const double* d_kappa, const uint8_t* d_edge_valid,
+                        int n_edges, int n_img, const double* d_wRi_init, uint64_t seed, int p_min, int p_max,
+                        double optimality_threshold, double grad_rel_tol, int max_iterations, double pcg_rel_tol,
+                        int pcg_max_iter, double eig_tol, int eig_max_steps, void* d_workspace, size_t workspace_bytes,
+                        double* d_wRi, uint8_t* d_rot_valid, double* d_stats, void* stream);
 
 #ifdef __cplusplus
 }
