@@ -37,6 +37,36 @@ static inline hipError_t gtsfm_set_dynamic_lds(const void* fn, int bytes) {
 
 __host__ __device__ static inline size_t gtsfm_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Workgroups of b lanes that cover n items.
+static inline unsigned blocks_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
+
+// Lays a device workspace out: take(bytes) is the offset of the next 256-byte aligned piece and `o` the bytes taken so
+// far. An empty piece still takes 256 bytes, so no two pieces share an address.
+struct WsCarver {
+    size_t o = 0;
+    size_t take(size_t bytes) {
+        const size_t at = o;
+        o += gtsfm_align_up(bytes ? bytes : 1, 256);
+        return at;
+    }
+};
+
+// Reads count elements back from the device on `stream` and waits for them.
+template <class T>
+static inline int read_back(T* host, const T* dev, size_t count, hipStream_t stream) {
+    GTSFM_CHECK_HIP(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, stream));
+    GTSFM_CHECK_HIP(hipStreamSynchronize(stream));
+    return GTSFM_OK;
+}
+
+// Relaxed agent-scope load and store of an int that other lanes change with atomics while the kernel runs.
+__device__ __forceinline__ int ld_int(const int* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_int(int* p, int v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Lane-wise min/max/median of three unsigned keys (v_min_u32 / v_med3_u32).
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }

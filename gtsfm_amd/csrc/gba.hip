@@ -4,7 +4,7 @@
 // gtsfm/bundle/global_ba.py and gtsfm/common/gtsfm_data.py:389-427 (filter_landmarks), on GTSAM 4.2's
 // LevenbergMarquardtOptimizer. The factors, the priors, the retraction, the cheirality treatment and the LM schedule
 // are ba2.hip's, generalised from two cameras (camera 0 = identity) to N cameras with an arbitrary first camera; the
-// SO(3) / SE(3) helpers below repeat ba2.hip's. Calibration is held fixed (k1 = k2 = 0), as ba2.hip:19-22 states.
+// SO(3) / SE(3) helpers are se3.hpp's for both. Calibration is held fixed (k1 = k2 = 0), as ba2.hip:19-22 states.
 //
 // What differs from ba2.hip is the linear solve. The 6C x 6C reduced camera system is never formed: each LM trial
 // eliminates the points (3 x 3 blocks, damped) and solves S dc = b by preconditioned conjugate gradients from a zero
@@ -15,9 +15,10 @@
 //   gba_prod_cams    one 256-lane workgroup per camera, walking the camera-major index built once per call by a stable
 //                    counting sort:                   q_c = (Hcc_c + lambda I) p_c - sum_m Jx_m^T (Jp_m y_track(m))
 //   gba_pcg_step     one workgroup: the dot products, x, r, z = M^-1 r, p.
-// Every sum has a fixed order (a lane's strided partial, a 64-lane butterfly, the waves in order), there is no
-// floating-point atomic, so two calls return the same bytes. The LM and PCG control flow is host code: one small
-// device-to-host read per PCG iteration and per LM trial, so this entry point synchronises its stream.
+// Every sum has a fixed order (a lane's strided partial, a 64-lane butterfly, the waves in order: reduce.hpp), there is
+// no floating-point atomic, so two calls return the same bytes. The LM and PCG control flow is host code (its decisions
+// are lm.hpp's): one small device-to-host read per PCG iteration and per LM trial, so this entry point synchronises its
+// stream.
 #include <limits.h>
 #include <math.h>
 
@@ -25,15 +26,15 @@
 
 #pragma clang fp contract(off)
 
+#include "csr.hpp"
+#include "lm.hpp"
+#include "reduce.hpp"
+#include "se3.hpp"
+
 namespace {
 
-constexpr double kHuberK = 1.345;
-constexpr double kMinFidelity = 1e-3;
-constexpr double kLambdaUpper = 1e5;
-constexpr double kDblEps = 2.220446049250313e-16;
 constexpr double kPointPriorW = 100.0;  // PriorFactorPoint3 sigma 0.1
-constexpr int kInnerMax = 64;
-constexpr int kLin = 20;        // doubles per measurement: Jx[12], Jp[6], b[2]
+constexpr int kLin = 20;       // doubles per measurement: Jx[12], Jp[6], b[2]
 constexpr int kCamBlock = 256;  // lanes of a camera-grouped workgroup
 constexpr int kVecBlock = 1024; // lanes of the single-workgroup vector kernels
 constexpr int kSortChunksMax = 1024;
@@ -42,117 +43,6 @@ constexpr int kSortChunksMax = 1024;
 enum { S_RR = 0, S_RZ = 1, S_BB = 2, S_OLDLIN = 3, S_NEWLIN = 4, S_NEWERR = 5, S_XI0 = 8, S_COUNT = 16 };
 // icnt[] slots (ints, device)
 enum { I_NPART = 0, I_NMOD = 1, I_T0 = 2, I_C0 = 3, I_NFAC = 4, I_NKEPT = 5, I_BAD = 6, I_COUNT = 8 };
-
-struct Pose {
-    double R[9];  // wRc row-major
-    double t[3];  // wtc
-};
-
-__device__ __forceinline__ void skew3(const double* w, double* S) {
-    S[0] = 0; S[1] = -w[2]; S[2] = w[1];
-    S[3] = w[2]; S[4] = 0; S[5] = -w[0];
-    S[6] = -w[1]; S[7] = w[0]; S[8] = 0;
-}
-
-__device__ __forceinline__ void mm3(const double* A, const double* B, double* C) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-
-__device__ __forceinline__ void mtv3(const double* A, const double* v, double* o) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) o[j] = A[j] * v[0] + A[3 + j] * v[1] + A[6 + j] * v[2];
-}
-
-__device__ __forceinline__ void mv3(const double* A, const double* v, double* o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = A[3 * i] * v[0] + A[3 * i + 1] * v[1] + A[3 * i + 2] * v[2];
-}
-
-__device__ void so3_exp(const double* w, double* R) {
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double W[9], W2[9];
-    skew3(w, W);
-    mm3(W, W, W2);
-    double a, b;
-    if (th2 < 1e-16) {
-        a = 1.0 - th2 / 6.0;
-        b = 0.5 - th2 / 24.0;
-    } else {
-        const double th = sqrt(th2);
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / th2;
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0 ? 1.0 : 0.0) + a * W[k] + b * W2[k];
-}
-
-__device__ void so3_log(const double* R, double* w) {
-    double c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
-    c = fmin(1.0, fmax(-1.0, c));
-    const double th = acos(c);
-    const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-    if (th < 1e-8) {
-        for (int k = 0; k < 3; ++k) w[k] = 0.5 * v[k];
-    } else if (3.14159265358979323846 - th < 1e-6) {
-        const int i = (R[0] >= R[4] && R[0] >= R[8]) ? 0 : (R[4] >= R[8] ? 1 : 2);
-        double ax[3];
-        ax[i] = sqrt(fmax(0.0, (R[4 * i] + 1.0) * 0.5));
-        for (int j = 0; j < 3; ++j)
-            if (j != i) ax[j] = (R[3 * i + j] + R[3 * j + i]) / (4.0 * ax[i]);
-        const double n = sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-        for (int k = 0; k < 3; ++k) w[k] = th * ax[k] / n;
-    } else {
-        const double s = th / (2.0 * sin(th));
-        for (int k = 0; k < 3; ++k) w[k] = s * v[k];
-    }
-}
-
-__device__ void pose_retract(const Pose& X, const double* xi, Pose& o) {
-    double dR[9], tv[3], W[9], W2[9];
-    so3_exp(xi, dR);
-    const double* w = xi;
-    const double* v = xi + 3;
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    skew3(w, W);
-    mm3(W, W, W2);
-    double a, b;
-    if (th2 < 1e-16) {
-        a = 0.5 - th2 / 24.0;
-        b = 1.0 / 6.0 - th2 / 120.0;
-    } else {
-        const double th = sqrt(th2);
-        a = (1.0 - cos(th)) / th2;
-        b = (th - sin(th)) / (th2 * th);
-    }
-    for (int i = 0; i < 3; ++i)
-        tv[i] = v[i] + a * (W[3 * i] * v[0] + W[3 * i + 1] * v[1] + W[3 * i + 2] * v[2]) +
-                b * (W2[3 * i] * v[0] + W2[3 * i + 1] * v[1] + W2[3 * i + 2] * v[2]);
-    mm3(X.R, dR, o.R);
-    double Rt[3];
-    mv3(X.R, tv, Rt);
-    for (int i = 0; i < 3; ++i) o.t[i] = X.t[i] + Rt[i];
-}
-
-__device__ void pose_log(const Pose& T, double* xi) {
-    double w[3];
-    so3_log(T.R, w);
-    const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    xi[0] = w[0]; xi[1] = w[1]; xi[2] = w[2];
-    if (th < 1e-10) {
-        for (int k = 0; k < 3; ++k) xi[3 + k] = T.t[k];
-        return;
-    }
-    double W[9], Wt[3], WWt[3];
-    const double wn[3] = {w[0] / th, w[1] / th, w[2] / th};
-    skew3(wn, W);
-    mv3(W, T.t, Wt);
-    mv3(W, Wt, WWt);
-    const double tn = tan(0.5 * th);
-    for (int k = 0; k < 3; ++k) xi[3 + k] = T.t[k] - (0.5 * th) * Wt[k] + (1.0 - th / (2.0 * tn)) * WWt[k];
-}
 
 // Logmap(A^-1 B): the pose prior's residual at B for a prior at A (ba2.hip has A = identity)
 __device__ void pose_local(const Pose& A, const Pose& B, double* xi) {
@@ -163,55 +53,6 @@ __device__ void pose_local(const Pose& A, const Pose& B, double* xi) {
     const double d[3] = {B.t[0] - A.t[0], B.t[1] - A.t[1], B.t[2] - A.t[2]};
     mtv3(A.R, d, T.t);
     pose_log(T, xi);
-}
-
-__device__ __forceinline__ bool project(const Pose& X, const double* K, const double* p, double* pc, double* uv) {
-    const double d[3] = {p[0] - X.t[0], p[1] - X.t[1], p[2] - X.t[2]};
-    mtv3(X.R, d, pc);
-    if (pc[2] <= 0.0) return false;
-    uv[0] = K[1] + K[0] * (pc[0] / pc[2]);
-    uv[1] = K[2] + K[0] * (pc[1] / pc[2]);
-    return true;
-}
-
-__device__ __forceinline__ void project_jac(const Pose& X, const double* K, const double* pc, double* Jp, double* Jx) {
-    const double iz = 1.0 / pc[2], xn = pc[0] * iz, yn = pc[1] * iz, f = K[0];
-    const double D[6] = {f * iz, 0.0, -f * xn * iz, 0.0, f * iz, -f * yn * iz};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            Jp[3 * r + j] = D[3 * r] * X.R[3 * j] + D[3 * r + 1] * X.R[3 * j + 1] + D[3 * r + 2] * X.R[3 * j + 2];
-        const double* d = D + 3 * r;
-        Jx[6 * r + 0] = d[1] * pc[2] - d[2] * pc[1];
-        Jx[6 * r + 1] = -d[0] * pc[2] + d[2] * pc[0];
-        Jx[6 * r + 2] = d[0] * pc[1] - d[1] * pc[0];
-        Jx[6 * r + 3] = -d[0];
-        Jx[6 * r + 4] = -d[1];
-        Jx[6 * r + 5] = -d[2];
-    }
-}
-
-__device__ __forceinline__ double huber_loss(double d) {
-    return d <= kHuberK ? 0.5 * d * d : kHuberK * d - 0.5 * kHuberK * kHuberK;
-}
-__device__ __forceinline__ double huber_weight(double d) { return d <= kHuberK ? 1.0 : kHuberK / d; }
-
-__device__ bool inv3(const double* A, double* I) {
-    const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
-    const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
-    if (!(fabs(det) > 0.0) || !isfinite(det)) return false;
-    const double id = 1.0 / det;
-    I[0] = c00 * id;
-    I[1] = (A[2] * A[7] - A[1] * A[8]) * id;
-    I[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-    I[3] = c01 * id;
-    I[4] = (A[0] * A[8] - A[2] * A[6]) * id;
-    I[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-    I[6] = c02 * id;
-    I[7] = (A[1] * A[6] - A[0] * A[7]) * id;
-    I[8] = (A[0] * A[4] - A[1] * A[3]) * id;
-    return true;
 }
 
 // inverse of a symmetric positive definite 6 x 6 (full storage) by Cholesky; false when it is not positive definite
@@ -245,27 +86,6 @@ __device__ bool spd6_inverse(const double* S, double* Inv) {
         for (int i = 0; i < 6; ++i) Inv[6 * i + c] = s[i];
     }
     return true;
-}
-
-// Sum of v[0..NV) over the workgroup (a multiple of 64 lanes, at most 1024), the same on every lane: 64-lane butterfly,
-// then the waves in order. sh holds 16 * NV doubles.
-template <int NV>
-__device__ __forceinline__ void block_sum(double* v, double* sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    }
-    if (lane == 0)
-        for (int k = 0; k < NV; ++k) sh[wave * NV + k] = v[k];
-    __syncthreads();
-    for (int k = 0; k < NV; ++k) {
-        double s = sh[k];
-        for (int w = 1; w < nw; ++w) s += sh[w * NV + k];
-        v[k] = s;
-    }
-    __syncthreads();
 }
 
 struct GbaArgs {
@@ -315,7 +135,7 @@ struct GbaArgs {
     double* p;
     double* q;
     double* scal;       // [S_COUNT]
-    int n_chunks, chunk;
+    CsrChunks chunks;   // of the sort by camera
 };
 
 __device__ __forceinline__ int n_tracks_eff(const GbaArgs& a) {
@@ -399,51 +219,19 @@ __global__ void gba_setup_cams(GbaArgs a) {
     atomicMin(&a.icnt[I_C0], c);
 }
 
-// stable counting sort of the factor measurements by camera: chunk-private histograms, a column scan, a scatter
-__global__ void gba_sort_hist(GbaArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n_chunks) return;
-    int* h = a.hist + (size_t)j * a.C;
-    const long long b = (long long)j * a.chunk;
-    const long long e = b + a.chunk < (long long)a.M ? b + a.chunk : (long long)a.M;
-    for (long long m = b; m < e; ++m)
-        if (a.mtrack[m] >= 0) ++h[a.img[m]];
-}
-
-__global__ void gba_sort_colscan(GbaArgs a) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.C) return;
-    int run = 0;
-    for (int j = 0; j < a.n_chunks; ++j) {
-        const int v = a.hist[(size_t)j * a.C + c];
-        a.hist[(size_t)j * a.C + c] = run;
-        run += v;
+// csr.hpp source: the factor measurements grouped by camera, perm[] their camera-major order
+struct GbaByCamera {
+    static constexpr int kKeys = 1;
+    const int* mtrack;
+    const int* img;
+    int* perm;
+    __device__ bool keys(long long m, int* k) const {
+        if (mtrack[m] < 0) return false;
+        k[0] = img[m];
+        return true;
     }
-    a.cam_off[c + 1] = run;  // the camera's count; gba_sort_camscan turns the counts into offsets
-}
-
-__global__ void gba_sort_camscan(GbaArgs a) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int run = 0;
-    a.cam_off[0] = 0;
-    for (int c = 0; c < a.C; ++c) {
-        run += a.cam_off[c + 1];
-        a.cam_off[c + 1] = run;
-    }
-}
-
-__global__ void gba_sort_scatter(GbaArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n_chunks) return;
-    int* h = a.hist + (size_t)j * a.C;
-    const long long b = (long long)j * a.chunk;
-    const long long e = b + a.chunk < (long long)a.M ? b + a.chunk : (long long)a.M;
-    for (long long m = b; m < e; ++m)
-        if (a.mtrack[m] >= 0) {
-            const int c = a.img[m];
-            a.perm[a.cam_off[c] + h[c]++] = (int)m;
-        }
-}
+    __device__ void put(long long m, const int*, const size_t* slot) const { perm[slot[0]] = (int)m; }
+};
 
 // ------------------------------------------------------------------ nonlinear error of (X, P): per-track partials
 __device__ double track_error(const GbaArgs& a, const double* X, const double* p, int t, int b, int e) {
@@ -929,7 +717,7 @@ __global__ void gba_stats(GbaArgs a, double* stats, double err0, double err, dou
 struct GbaLayout {
     size_t part, modelled, mtrack, cam_off, perm, hist, icnt, XA, XB, PA, PB, lin, Hcc, gc, Pinv, Hpp, Minv, rp, y, tl,
         te, vec, scal, total;
-    int n_chunks, chunk;
+    CsrChunks chunks;
 };
 
 bool gba_sizes_ok(long long n_tracks, long long n_meas, int n_img) {
@@ -939,43 +727,35 @@ bool gba_sizes_ok(long long n_tracks, long long n_meas, int n_img) {
 
 GbaLayout gba_layout(long long T, long long M, int C) {
     GbaLayout L;
-    L.n_chunks = (int)((M + 63) / 64 < kSortChunksMax ? (M + 63) / 64 : kSortChunksMax);
-    L.chunk = (int)((M + L.n_chunks - 1) / L.n_chunks);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += gtsfm_align_up(bytes, 256);
-        return at;
-    };
+    L.chunks = csr_chunks(M, kSortChunksMax);
+    WsCarver w;
     const size_t t = (size_t)T, m = (size_t)M, c = (size_t)C, d = sizeof(double);
-    L.part = take(t);
-    L.modelled = take(c);
-    L.mtrack = take(m * 4);
-    L.cam_off = take((c + 1) * 4);
-    L.perm = take(m * 4);
-    L.hist = take((size_t)L.n_chunks * c * 4);
-    L.icnt = take(I_COUNT * 4);
-    L.XA = take(c * 12 * d);
-    L.XB = take(c * 12 * d);
-    L.PA = take(t * 3 * d);
-    L.PB = take(t * 3 * d);
-    L.lin = take(m * kLin * d);
-    L.Hcc = take(c * 36 * d);
-    L.gc = take(c * 6 * d);
-    L.Pinv = take(c * 36 * d);
-    L.Hpp = take(t * 9 * d);
-    L.Minv = take(t * 9 * d);
-    L.rp = take(t * 3 * d);
-    L.y = take(t * 3 * d);
-    L.tl = take(t * d);
-    L.te = take(t * d);
-    L.vec = take(6 * c * 6 * d);
-    L.scal = take(S_COUNT * d);
-    L.total = o;
+    L.part = w.take(t);
+    L.modelled = w.take(c);
+    L.mtrack = w.take(m * 4);
+    L.cam_off = w.take((c + 1) * 4);
+    L.perm = w.take(m * 4);
+    L.hist = w.take(csr_hist_bytes(L.chunks, c));
+    L.icnt = w.take(I_COUNT * 4);
+    L.XA = w.take(c * 12 * d);
+    L.XB = w.take(c * 12 * d);
+    L.PA = w.take(t * 3 * d);
+    L.PB = w.take(t * 3 * d);
+    L.lin = w.take(m * kLin * d);
+    L.Hcc = w.take(c * 36 * d);
+    L.gc = w.take(c * 6 * d);
+    L.Pinv = w.take(c * 36 * d);
+    L.Hpp = w.take(t * 9 * d);
+    L.Minv = w.take(t * 9 * d);
+    L.rp = w.take(t * 3 * d);
+    L.y = w.take(t * 3 * d);
+    L.tl = w.take(t * d);
+    L.te = w.take(t * d);
+    L.vec = w.take(6 * c * 6 * d);
+    L.scal = w.take(S_COUNT * d);
+    L.total = w.o;
     return L;
 }
-
-inline unsigned blocks_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace
 
@@ -1049,23 +829,15 @@ int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const vo
     const size_t n6 = 6 * (size_t)C;
     a.bvec = vec; a.x = vec + n6; a.r = vec + 2 * n6; a.z = vec + 3 * n6; a.p = vec + 4 * n6; a.q = vec + 5 * n6;
     a.scal = (double*)(ws + L.scal);
-    a.n_chunks = L.n_chunks; a.chunk = L.chunk;
+    a.chunks = L.chunks;
 
     const unsigned B = 256;
     const unsigned gT = blocks_for(T, B), gM = blocks_for(M, B), gC = blocks_for(C, B);
     const size_t nmax = (size_t)(T > M ? T : M) > (size_t)C ? (size_t)(T > M ? T : M) : (size_t)C;
     int icnt[I_COUNT];
     double scal[6];
-    auto read_icnt = [&]() -> int {
-        GTSFM_CHECK_HIP(hipMemcpyAsync(icnt, a.icnt, sizeof(icnt), hipMemcpyDeviceToHost, stream));
-        GTSFM_CHECK_HIP(hipStreamSynchronize(stream));
-        return GTSFM_OK;
-    };
-    auto read_scal = [&]() -> int {
-        GTSFM_CHECK_HIP(hipMemcpyAsync(scal, a.scal, sizeof(scal), hipMemcpyDeviceToHost, stream));
-        GTSFM_CHECK_HIP(hipStreamSynchronize(stream));
-        return GTSFM_OK;
-    };
+    auto read_icnt = [&]() { return read_back(icnt, a.icnt, I_COUNT, stream); };
+    auto read_scal = [&]() { return read_back(scal, a.scal, 6, stream); };
 
     hipLaunchKernelGGL(gba_init, dim3(blocks_for(nmax, B)), dim3(B), 0, stream, a);
     hipLaunchKernelGGL(gba_setup_tracks, dim3(gT), dim3(B), 0, stream, a);
@@ -1075,11 +847,8 @@ int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const vo
     if (rc != GTSFM_OK) return rc;
     if (icnt[I_NPART] == 0 || icnt[I_NMOD] == 0) return copy_through();
 
-    GTSFM_CHECK_HIP(hipMemsetAsync(a.hist, 0, (size_t)L.n_chunks * C * sizeof(int), stream));
-    hipLaunchKernelGGL(gba_sort_hist, dim3(blocks_for(L.n_chunks, 64)), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(gba_sort_colscan, dim3(gC), dim3(B), 0, stream, a);
-    hipLaunchKernelGGL(gba_sort_camscan, dim3(1), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(gba_sort_scatter, dim3(blocks_for(L.n_chunks, 64)), dim3(64), 0, stream, a);
+    if ((rc = csr_build(GbaByCamera{a.mtrack, a.img, a.perm}, M, C, a.chunks, a.hist, a.cam_off, stream)) != GTSFM_OK)
+        return rc;
 
     double* X = a.XA;
     double* Xn = a.XB;
@@ -1110,60 +879,40 @@ int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const vo
                 hipLaunchKernelGGL(gba_pcg_init, dim3(1), dim3(kVecBlock), 0, stream, a);
                 GTSFM_CHECK_HIP(hipGetLastError());
                 if ((rc = read_icnt()) != GTSFM_OK) return rc;
-                bool success = false, stop = false;
-                double newErr = INFINITY;
+                LmTrial trial;
                 if (!icnt[I_BAD]) {
                     if ((rc = read_scal()) != GTSFM_OK) return rc;
                     if (!have_oldlin) {
                         oldLin = scal[S_OLDLIN];
                         have_oldlin = true;
                     }
-                    const double bb = scal[S_BB];
-                    double rr = scal[S_RR];
-                    int k = 0;
-                    // ||r|| <= tol ||b||; a non-finite residual ends the solve, the step then fails the accept test
-                    while (isfinite(rr) && !(sqrt(rr) <= pcg_rel_tol * sqrt(bb))) {
-                        if (k >= pcg_max_iter) {
-                            ++cap_hits;
-                            break;
-                        }
+                    rc = pcg_iterate(scal[S_BB], scal[S_RR], pcg_rel_tol, pcg_max_iter, pcg_total, cap_hits,
+                                     [&](double& rr) -> int {
                         hipLaunchKernelGGL(gba_prod_tracks, dim3(gT), dim3(B), 0, stream, a);
                         hipLaunchKernelGGL(gba_prod_cams, dim3(C), dim3(kCamBlock), 0, stream, a, lambda);
                         hipLaunchKernelGGL(gba_pcg_step, dim3(1), dim3(kVecBlock), 0, stream, a);
                         GTSFM_CHECK_HIP(hipGetLastError());
-                        if ((rc = read_scal()) != GTSFM_OK) return rc;
+                        const int rc2 = read_scal();
                         rr = scal[S_RR];
-                        ++k;
-                    }
-                    pcg_total += k;
+                        return rc2;
+                    });
+                    if (rc != GTSFM_OK) return rc;
                     hipLaunchKernelGGL(gba_retract, dim3(gC), dim3(B), 0, stream, a, X, Xn);
                     hipLaunchKernelGGL(gba_backsub, dim3(gT), dim3(B), 0, stream, a, Xn, P, Pn);
                     hipLaunchKernelGGL(gba_reduce, dim3(1), dim3(kVecBlock), 0, stream, a, Xn, 1);
                     GTSFM_CHECK_HIP(hipGetLastError());
                     if ((rc = read_scal()) != GTSFM_OK) return rc;
-                    const double newLin = scal[S_NEWLIN], linChange = oldLin - newLin;
-                    if (linChange >= 0) {
-                        newErr = scal[S_NEWERR];
-                        const double costChange = err - newErr;
-                        if (linChange > kDblEps * oldLin) success = costChange / linChange > kMinFidelity;
-                        else success = true;
-                        if (fabs(costChange) < 1e-5 * err) stop = true;
-                    }
+                    trial = lm_judge(err, oldLin, scal[S_NEWLIN], scal[S_NEWERR]);
                 }
-                if (success) {
+                if (trial.success) {
                     double* s = X; X = Xn; Xn = s;
                     s = P; P = Pn; Pn = s;
-                    err = newErr;
-                    lambda /= 10.0;
+                    err = trial.newErr;
                     ++iters;
-                    break;
                 }
-                if (stop) break;
-                lambda *= 10.0;
-                if (lambda >= kLambdaUpper) break;
+                if (lm_trials_done(trial, lambda)) break;
             }
-            const double dec = cur - err;
-            if (iters >= max_iters || dec / cur <= 1e-5 || dec <= 1e-5 || !isfinite(cur)) break;
+            if (lm_done(cur, err, iters, max_iters)) break;
         }
     }
     GTSFM_CHECK_HIP(hipMemsetAsync(d_track_keep, 0, (size_t)T, stream));

@@ -5,7 +5,7 @@
 //
 // The cost tr(Y Q Y') is quadratic in the lifted variable, so the gradient, the Hessian-vector product and the
 // certificate's operator are all Out = V Q with Q the 3n x 3n connection Laplacian: ra_matvec, the hot kernel. Q is a
-// node-major list of half-edges in ascending edge index (a stable counting sort, as transavg.hip's), each entry a
+// node-major list of half-edges in ascending edge index (the stable counting sort of csr.hpp), each entry a
 // neighbour, a 3 x 3 block (aRb' on the a side, aRb on the b side) and kappa, 80 + 4 bytes. One wave owns one node: its
 // 64 lanes are (slice, row) pairs, floor(64 / p) slices of p rows; a lane walks the half-edges slice, slice + slices,
 // ... of the node's list for its row of V and the slices are added in a fixed tree in LDS, so a hub camera's list is
@@ -18,6 +18,9 @@
 #include "twoview.hpp"  // sm_mix, jacobi_eig_reg, svd3, det3
 
 #pragma clang fp contract(off)
+
+#include "csr.hpp"
+#include "reduce.hpp"  // uf_find, uf_unite
 
 namespace {
 
@@ -37,17 +40,14 @@ constexpr double kAlphaMin = 1e-2;  // initializeWithDescent's smallest step
 enum { I_NKEPT = 0, I_NEG, I_COUNT = 4 };
 enum { S_DOT = 0, S_RZ, S_RR, S_NEG, S_GX, S_XQ, S_XDX, S_ALPHA, S_BETA, S_D2, S_COUNT = 16 };
 
-inline unsigned blocks_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
-__device__ __forceinline__ int ld_int(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 struct Args {
     const int* edges;       // [E][2] (a, b)
     const double* aRb;      // [E][9]
     const double* kappa;    // [E] or NULL
     const uint8_t* evalid;  // [E] or NULL
     const double* init;     // [n_img][9] or NULL
-    int E, n_img, n_chunks, chunk;
+    int E, n_img;
+    CsrChunks chunks;
     uint64_t seed;
     uint8_t* use;    // [E]
     int* parent;     // [n_img]
@@ -68,23 +68,7 @@ struct Args {
 };
 
 // ------------------------------------------------------------------ setup: edges, components, remap, half-edge lists
-__device__ int uf_find(int* p, int x) {
-    int y;
-    while ((y = ld_int(p + x)) != x) x = y;
-    return x;
-}
-
-// links the larger root under the smaller: a component's root is its lowest camera index (tracks.hip's rule)
-__device__ void uf_unite(int* p, int a, int b) {
-    for (;;) {
-        a = uf_find(p, a);
-        b = uf_find(p, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        if (atomicCAS(p + a, a, b) == a) return;
-    }
-}
-
+// The components are reduce.hpp's union-find: a component's root is its lowest camera index.
 __global__ void ra_init(Args a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < I_COUNT) a.icnt[i] = 0;
@@ -141,68 +125,38 @@ __global__ void ra_edge_remap(Args a) {
     a.rkey[2 * e + 1] = ok ? a.newidx[a.edges[2 * e + 1]] : -1;
 }
 
-__global__ void ra_csr_hist(Args a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n_chunks) return;
-    int* h = a.hist + (size_t)j * a.n_img;
-    const long long b = (long long)j * a.chunk;
-    const long long e = b + a.chunk < (long long)a.E ? b + a.chunk : (long long)a.E;
-    for (long long m = b; m < e; ++m)
-        if (a.use[m]) {
-            ++h[a.rkey[2 * m]];
-            ++h[a.rkey[2 * m + 1]];
-        }
-}
-
-__global__ void ra_csr_colscan(Args a) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= a.n_img) return;
-    int run = 0;
-    for (int j = 0; j < a.n_chunks; ++j) {
-        const int c = a.hist[(size_t)j * a.n_img + v];
-        a.hist[(size_t)j * a.n_img + v] = run;
-        run += c;
+// csr.hpp source. Half-edge of edge (a, b, R, kappa): at a the neighbour b with block R', at b the neighbour a with
+// block R, so that (V Q)_i = sum_h kappa_h (V_i - V_nbr(h) block_h)
+struct HalfEdges {
+    static constexpr int kKeys = 2;
+    const uint8_t* use;
+    const int* rkey;
+    const double* aRb;
+    const double* kappa;
+    int* nbr;
+    double* blk;
+    __device__ bool keys(long long m, int* k) const {
+        if (!use[m]) return false;
+        k[0] = rkey[2 * m];
+        k[1] = rkey[2 * m + 1];
+        return true;
     }
-    a.node_off[v + 1] = run;
-}
-
-__global__ void ra_csr_scan(Args a) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int run = 0;
-    a.node_off[0] = 0;
-    for (int v = 0; v < a.n_img; ++v) {
-        run += a.node_off[v + 1];
-        a.node_off[v + 1] = run;
+    __device__ void put(long long m, const int* k, const size_t* slot) const {
+        const double* R = aRb + 9 * (size_t)m;
+        const double kap = kappa ? kappa[m] : 1.0;
+        nbr[slot[0]] = k[1];
+        nbr[slot[1]] = k[0];
+        double* ba = blk + slot[0] * kEntry;
+        double* bb = blk + slot[1] * kEntry;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                ba[3 * r + c] = R[3 * c + r];
+                bb[3 * r + c] = R[3 * r + c];
+            }
+        ba[9] = kap;
+        bb[9] = kap;
     }
-}
-
-// half-edge of edge (a, b, R, kappa): at a the neighbour b with block R', at b the neighbour a with block R, so that
-// (V Q)_i = sum_h kappa_h (V_i - V_nbr(h) block_h)
-__global__ void ra_csr_scatter(Args a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n_chunks) return;
-    int* h = a.hist + (size_t)j * a.n_img;
-    const long long b = (long long)j * a.chunk;
-    const long long e = b + a.chunk < (long long)a.E ? b + a.chunk : (long long)a.E;
-    for (long long m = b; m < e; ++m)
-        if (a.use[m]) {
-            const int ka = a.rkey[2 * m], kb = a.rkey[2 * m + 1];
-            const double* R = a.aRb + 9 * (size_t)m;
-            const double kap = a.kappa ? a.kappa[m] : 1.0;
-            const size_t ha = (size_t)a.node_off[ka] + h[ka]++, hb = (size_t)a.node_off[kb] + h[kb]++;
-            a.nbr[ha] = kb;
-            a.nbr[hb] = ka;
-            double* ba = a.blk + ha * kEntry;
-            double* bb = a.blk + hb * kEntry;
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) {
-                    ba[3 * r + c] = R[3 * c + r];
-                    bb[3 * r + c] = R[3 * r + c];
-                }
-            ba[9] = kap;
-            bb[9] = kap;
-        }
-}
+};
 
 __global__ void ra_degree(Args a, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -645,42 +599,40 @@ void host_jacobi(double* A, int n, double* w, double* V) {
 struct Layout {
     size_t use, parent, cnt, hase, keep, newidx, old, icnt, rkey, node_off, hist, nbr, blk, D, Lam, scal, vec, basis, lw,
         lv, lc, gram, B, total;
-    int n_chunks, chunk;
+    CsrChunks chunks;
 };
 
 constexpr int kVecs = 9;  // Y, Yn, G, Gn, g, x, r, pv, q
 
 Layout layout(int E, int n_img, int p_max) {
     Layout L;
-    L.n_chunks = (int)((E + 63) / 64 < kChunksMax ? (E + 63) / 64 : kChunksMax);
-    L.chunk = (E + L.n_chunks - 1) / L.n_chunks;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += gtsfm_align_up(bytes ? bytes : 1, 256); return at; };
+    L.chunks = csr_chunks(E, kChunksMax);
+    WsCarver w;
     const size_t e = (size_t)E, n = (size_t)n_img, d = sizeof(double);
-    L.use = take(e);
-    L.parent = take(n * 4);
-    L.cnt = take(n * 4);
-    L.hase = take(n);
-    L.keep = take(n);
-    L.newidx = take(n * 4);
-    L.old = take(n * 4);
-    L.icnt = take(I_COUNT * 4);
-    L.rkey = take(e * 8);
-    L.node_off = take((n + 1) * 4);
-    L.hist = take((size_t)L.n_chunks * n * 4);
-    L.nbr = take(2 * e * 4);
-    L.blk = take(2 * e * kEntry * d);
-    L.D = take(n * d);
-    L.Lam = take(n * 9 * d);
-    L.scal = take(S_COUNT * d);
-    L.vec = take((size_t)kVecs * n * p_max * 3 * d);
-    L.basis = take((size_t)(kLanczosMax + 1) * n * 3 * d);
-    L.lw = take(n * 3 * d);
-    L.lv = take(n * 3 * d);
-    L.lc = take((kLanczosMax + 1) * d);
-    L.gram = take((size_t)kPMax * kPMax * d);
-    L.B = take(n * 9 * d);
-    L.total = o;
+    L.use = w.take(e);
+    L.parent = w.take(n * 4);
+    L.cnt = w.take(n * 4);
+    L.hase = w.take(n);
+    L.keep = w.take(n);
+    L.newidx = w.take(n * 4);
+    L.old = w.take(n * 4);
+    L.icnt = w.take(I_COUNT * 4);
+    L.rkey = w.take(e * 8);
+    L.node_off = w.take((n + 1) * 4);
+    L.hist = w.take(csr_hist_bytes(L.chunks, n));
+    L.nbr = w.take(2 * e * 4);
+    L.blk = w.take(2 * e * kEntry * d);
+    L.D = w.take(n * d);
+    L.Lam = w.take(n * 9 * d);
+    L.scal = w.take(S_COUNT * d);
+    L.vec = w.take((size_t)kVecs * n * p_max * 3 * d);
+    L.basis = w.take((size_t)(kLanczosMax + 1) * n * 3 * d);
+    L.lw = w.take(n * 3 * d);
+    L.lv = w.take(n * 3 * d);
+    L.lc = w.take((kLanczosMax + 1) * d);
+    L.gram = w.take((size_t)kPMax * kPMax * d);
+    L.B = w.take(n * 9 * d);
+    L.total = w.o;
     return L;
 }
 
@@ -712,7 +664,7 @@ int gtsfm_rotavg_shonan(const int* d_edges, const double* d_aRb, const double* d
     unsigned char* ws = (unsigned char*)d_workspace;
     Args a;
     a.edges = d_edges; a.aRb = d_aRb; a.kappa = d_kappa; a.evalid = d_edge_valid; a.init = d_wRi_init;
-    a.E = n_edges; a.n_img = n_img; a.n_chunks = L.n_chunks; a.chunk = L.chunk; a.seed = seed;
+    a.E = n_edges; a.n_img = n_img; a.chunks = L.chunks; a.seed = seed;
     a.use = ws + L.use; a.parent = (int*)(ws + L.parent); a.cnt = (int*)(ws + L.cnt); a.hase = ws + L.hase;
     a.keep = ws + L.keep; a.newidx = (int*)(ws + L.newidx); a.old = (int*)(ws + L.old); a.icnt = (int*)(ws + L.icnt);
     a.rkey = (int*)(ws + L.rkey); a.node_off = (int*)(ws + L.node_off); a.hist = (int*)(ws + L.hist);
@@ -730,28 +682,21 @@ int gtsfm_rotavg_shonan(const int* d_edges, const double* d_aRb, const double* d
     double* Bk = (double*)(ws + L.B);
 
     const unsigned B = 256;
-    const unsigned gE = blocks_for(n_edges, B), gI = blocks_for(n_img, B), gC = blocks_for(L.n_chunks, 64);
+    const unsigned gE = blocks_for(n_edges, B), gI = blocks_for(n_img, B);
     int icnt[I_COUNT];
     double scal[S_COUNT];
-    auto read_scal = [&]() -> int {
-        GTSFM_CHECK_HIP(hipMemcpyAsync(scal, a.scal, sizeof(scal), hipMemcpyDeviceToHost, stream));
-        GTSFM_CHECK_HIP(hipStreamSynchronize(stream));
-        return GTSFM_OK;
-    };
+    auto read_scal = [&]() { return read_back(scal, a.scal, S_COUNT, stream); };
     int rc;
     GTSFM_CHECK_HIP(hipMemsetAsync(d_wRi, 0, (size_t)n_img * 9 * sizeof(double), stream));
     GTSFM_CHECK_HIP(hipMemsetAsync(d_rot_valid, 0, (size_t)n_img, stream));
-    GTSFM_CHECK_HIP(hipMemsetAsync(a.hist, 0, (size_t)L.n_chunks * n_img * sizeof(int), stream));
     hipLaunchKernelGGL(ra_init, dim3(gI), dim3(B), 0, stream, a);
     hipLaunchKernelGGL(ra_edge_use, dim3(gE), dim3(B), 0, stream, a);
     hipLaunchKernelGGL(ra_comp_count, dim3(gI), dim3(B), 0, stream, a);
     hipLaunchKernelGGL(ra_select, dim3(1), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(ra_edge_remap, dim3(gE), dim3(B), 0, stream, a);
-    hipLaunchKernelGGL(ra_csr_hist, dim3(gC), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(ra_csr_colscan, dim3(gI), dim3(B), 0, stream, a);
-    hipLaunchKernelGGL(ra_csr_scan, dim3(1), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(ra_csr_scatter, dim3(gC), dim3(64), 0, stream, a);
-    GTSFM_CHECK_HIP(hipGetLastError());
+    if ((rc = csr_build(HalfEdges{a.use, a.rkey, a.aRb, a.kappa, a.nbr, a.blk}, n_edges, n_img, a.chunks, a.hist,
+                        a.node_off, stream)) != GTSFM_OK)
+        return rc;
     GTSFM_CHECK_HIP(hipMemcpyAsync(icnt, a.icnt, sizeof(icnt), hipMemcpyDeviceToHost, stream));
     int half_edges = 0;
     GTSFM_CHECK_HIP(hipMemcpyAsync(&half_edges, a.node_off + n_img, sizeof(int), hipMemcpyDeviceToHost, stream));

@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "reduce.hpp"  // uf_unite
 
 namespace {
 
@@ -53,59 +54,21 @@ inline size_t tr_tiles(size_t N) { return (N + TR_SCAN_TILE - 1) / TR_SCAN_TILE;
 
 inline TrLayout tr_layout(size_t N) {
     TrLayout L;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) {
-        const size_t at = o;
-        o += gtsfm_align_up(bytes, 256);
-        return at;
-    };
-    L.cnt = take(N * 4);
-    L.bad = take(N);
-    L.touched = take(N);
-    L.counters = take(TR_COUNTER_BYTES);
-    L.zero_end = o;
-    L.parent = take(N * 4);
-    L.root = take(N * 4);
-    L.slot = take(N * 4);     // member slot, later the track index of a root
-    L.seg = take(N * 4);      // segment base of a root, later its measurement offset
-    L.members = take(N * 4);
-    L.rank = take(N * 4);
-    L.tile_sums = take(tr_tiles(N) * 2 * 4);
-    L.total = o;
+    WsCarver w;
+    L.cnt = w.take(N * 4);
+    L.bad = w.take(N);
+    L.touched = w.take(N);
+    L.counters = w.take(TR_COUNTER_BYTES);
+    L.zero_end = w.o;
+    L.parent = w.take(N * 4);
+    L.root = w.take(N * 4);
+    L.slot = w.take(N * 4);     // member slot, later the track index of a root
+    L.seg = w.take(N * 4);      // segment base of a root, later its measurement offset
+    L.members = w.take(N * 4);
+    L.rank = w.take(N * 4);
+    L.tile_sums = w.take(tr_tiles(N) * 2 * 4);
+    L.total = w.o;
     return L;
-}
-
-__device__ __forceinline__ int tr_load(const int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void tr_store(int* p, int v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Root of x with path halving. parent[y] <= y everywhere, so x strictly decreases until it is a root.
-__device__ __forceinline__ int tr_find(int* parent, int x) {
-    for (;;) {
-        const int p = tr_load(parent + x);
-        if (p == x) return x;
-        const int gp = tr_load(parent + p);
-        if (gp != p) tr_store(parent + x, gp);  // x is no root: only roots are CAS targets, so this races with none
-        x = gp;
-    }
-}
-
-__device__ __forceinline__ void tr_union(int* parent, int u, int v) {
-    int a = tr_find(parent, u), b = tr_find(parent, v);
-    while (a != b) {
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicCAS(parent + a, a, b);  // hook the larger root onto the smaller
-        if (old == a) return;
-        a = tr_find(parent, old);  // a was hooked by someone else meanwhile: old < a
-        b = tr_find(parent, b);
-    }
 }
 
 // Largest p in [lo, hi) with offsets[p] <= row, given offsets[lo] <= row.
@@ -159,7 +122,7 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_union_kernel(const int* __restric
         const int u = i1 * kmax + (int)k.x, v = i2 * kmax + (int)k.y;
         touched[u] = 1;
         touched[v] = 1;
-        tr_union(parent, u, v);
+        uf_unite(parent, u, v);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n_bad += __shfl_xor(n_bad, o, 64);

@@ -8,13 +8,14 @@
 // MFAS is the hot path: the reference runs its 2000 greedy orderings one after another in Python. Here one 256-lane
 // workgroup owns one projection direction; inSum, outSum and the removal position of every node live in LDS (20 bytes
 // per node), the graph is a node-major list of incident measurements built once per call by a stable counting sort
-// (gba.hip's), and an edge's weight is recomputed from its 24-byte direction wherever it is needed. The ordering is the
+// (csr.hpp), and an edge's weight is recomputed from its 24-byte direction wherever it is needed. The ordering is the
 // sequential one of the contract, one removal per step: a parallel search for the lowest source, else for the best
 // heuristic, then the removed node's incident edges in parallel (every neighbour is touched by one lane; a node with
 // two edges to the same neighbour is flagged at build time and updated by one lane in list order). The step count is
 // the node count by construction. The violated edges of a direction are kept as one bit each; one pass per edge then
-// adds the weights of its set bits in ascending direction order. The recovery reuses gba.hip's LM schedule, Huber
-// treatment, fixed-order reductions and matrix-free PCG with 3 x 3 blocks and no elimination.
+// adds the weights of its set bits in ascending direction order. The recovery shares gba.hip's LM schedule (lm.hpp),
+// Huber treatment (se3.hpp) and fixed-order reductions (reduce.hpp); its matrix-free PCG has 3 x 3 blocks and no
+// elimination.
 // fp64, no FMA contraction, no floating-point atomics: two calls return the same bytes.
 #include <limits.h>
 #include <math.h>
@@ -22,6 +23,11 @@
 #include "twoview.hpp"  // sm_mix
 
 #pragma clang fp contract(off)
+
+#include "csr.hpp"
+#include "lm.hpp"
+#include "reduce.hpp"
+#include "se3.hpp"  // mv3, inv3, Huber
 
 namespace {
 
@@ -32,16 +38,9 @@ constexpr int kVecBlock = 1024;
 constexpr int kNodeBlock = 256;  // 4 nodes per workgroup, one wave each
 constexpr int kChunksMax = 256;
 constexpr double kSourceEps = 1e-8;
-constexpr double kHuberK = 1.345;
 constexpr double kIsig = 100.0;    // 1 / NOISE_MODEL_SIGMA
 constexpr double kPriorW = 1.0e4;  // 1 / 0.01^2
-constexpr double kMinFidelity = 1e-3;
-constexpr double kLambdaUpper = 1e5;
-constexpr double kDblEps = 2.220446049250313e-16;
-constexpr int kInnerMax = 64;
 constexpr int kLin = 12;  // doubles per factor: A[9], b[3]
-
-inline unsigned blocks_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
@@ -56,16 +55,10 @@ __device__ __forceinline__ void unit3(const double* p, double* o) {
     }
 }
 
-__device__ __forceinline__ void rot3(const double* R, const double* v, double* o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
-}
-
-__device__ __forceinline__ int ld_int(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_int(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // ------------------------------------------------------------------ node-major incidence lists (stable counting sort)
+// csr.hpp source: every used measurement is listed at both of its nodes
 struct CsrArgs {
+    static constexpr int kKeys = 2;
     const int* key;      // [E][2]
     const uint8_t* use;  // [E]
     int E, n;
@@ -73,57 +66,18 @@ struct CsrArgs {
     int* inc;       // [2 E]
     int* hist;      // [chunks][n]
     uint8_t* dup;   // [n] or NULL
-    int n_chunks, chunk;
+    CsrChunks chunks;
+    __device__ bool keys(long long m, int* k) const {
+        if (!use[m]) return false;
+        k[0] = key[2 * m];
+        k[1] = key[2 * m + 1];
+        return true;
+    }
+    __device__ void put(long long m, const int*, const size_t* slot) const {
+        inc[slot[0]] = (int)m;
+        inc[slot[1]] = (int)m;
+    }
 };
-
-__global__ void ta_csr_hist(CsrArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n_chunks) return;
-    int* h = a.hist + (size_t)j * a.n;
-    const long long b = (long long)j * a.chunk;
-    const long long e = b + a.chunk < (long long)a.E ? b + a.chunk : (long long)a.E;
-    for (long long m = b; m < e; ++m)
-        if (a.use[m]) {
-            ++h[a.key[2 * m]];
-            ++h[a.key[2 * m + 1]];
-        }
-}
-
-__global__ void ta_csr_colscan(CsrArgs a) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= a.n) return;
-    int run = 0;
-    for (int j = 0; j < a.n_chunks; ++j) {
-        const int c = a.hist[(size_t)j * a.n + v];
-        a.hist[(size_t)j * a.n + v] = run;
-        run += c;
-    }
-    a.node_off[v + 1] = run;
-}
-
-__global__ void ta_csr_scan(CsrArgs a) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int run = 0;
-    a.node_off[0] = 0;
-    for (int v = 0; v < a.n; ++v) {
-        run += a.node_off[v + 1];
-        a.node_off[v + 1] = run;
-    }
-}
-
-__global__ void ta_csr_scatter(CsrArgs a) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n_chunks) return;
-    int* h = a.hist + (size_t)j * a.n;
-    const long long b = (long long)j * a.chunk;
-    const long long e = b + a.chunk < (long long)a.E ? b + a.chunk : (long long)a.E;
-    for (long long m = b; m < e; ++m)
-        if (a.use[m]) {
-            const int k1 = a.key[2 * m], k2 = a.key[2 * m + 1];
-            a.inc[a.node_off[k1] + h[k1]++] = (int)m;
-            a.inc[a.node_off[k2] + h[k2]++] = (int)m;
-        }
-}
 
 // dup[v] = 1 when two of v's incident measurements lead to the same neighbour
 __global__ void ta_csr_dup(CsrArgs a) {
@@ -143,14 +97,9 @@ __global__ void ta_csr_dup(CsrArgs a) {
     a.dup[v] = d;
 }
 
-int csr_chunks(long long E) { return (int)((E + 63) / 64 < kChunksMax ? (E + 63) / 64 : kChunksMax); }
-
-int csr_build(CsrArgs a, hipStream_t stream) {
-    GTSFM_CHECK_HIP(hipMemsetAsync(a.hist, 0, (size_t)a.n_chunks * a.n * sizeof(int), stream));
-    hipLaunchKernelGGL(ta_csr_hist, dim3(blocks_for(a.n_chunks, 64)), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(ta_csr_colscan, dim3(blocks_for(a.n, 256)), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(ta_csr_scan, dim3(1), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(ta_csr_scatter, dim3(blocks_for(a.n_chunks, 64)), dim3(64), 0, stream, a);
+int ta_csr_build(const CsrArgs& a, hipStream_t stream) {
+    const int rc = csr_build(a, a.E, a.n, a.chunks, a.hist, a.node_off, stream);
+    if (rc != GTSFM_OK) return rc;
     if (a.dup) hipLaunchKernelGGL(ta_csr_dup, dim3(blocks_for(a.n, 256)), dim3(256), 0, stream, a);
     GTSFM_CHECK_HIP(hipGetLastError());
     return GTSFM_OK;
@@ -219,7 +168,7 @@ __global__ void ta_cam_edges(MeasArgs a) {
     if (i1 < 0 || i1 >= a.n_img || i2 < 0 || i2 >= a.n_img || i1 == i2) return;
     if (a.rvalid && a.rvalid[i2] == 0) return;
     double w[3], u[3];
-    rot3(a.wRi + 9 * (size_t)i2, a.i2Ui1 + 3 * (size_t)e, w);
+    mv3(a.wRi + 9 * (size_t)i2, a.i2Ui1 + 3 * (size_t)e, w);
     unit3(w, u);
     a.key[2 * e] = i2;
     a.key[2 * e + 1] = i1;
@@ -334,7 +283,7 @@ __global__ void ta_track_dirs(MeasArgs a) {
         const double h[3] = {(uv[0] - K[1]) / K[0], (uv[1] - K[2]) / K[0], 1.0};
         double hu[3], w[3], u[3];
         unit3(h, hu);
-        rot3(a.wRi + 9 * (size_t)c, hu, w);
+        mv3(a.wRi + 9 * (size_t)c, hu, w);
         unit3(w, u);
         a.key[2 * slot] = c;
         a.key[2 * slot + 1] = a.n_img + s;
@@ -348,13 +297,12 @@ struct MeasLayout { size_t imp, remaining, mtrack, sel_off, total; };
 
 MeasLayout meas_layout(long long T, long long M, int C) {
     MeasLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += gtsfm_align_up(bytes ? bytes : 1, 256); return at; };
-    L.imp = take((size_t)T * 4);
-    L.remaining = take((size_t)C * 4);
-    L.mtrack = take((size_t)M * 4);
-    L.sel_off = take((size_t)T * 4);
-    L.total = o;
+    WsCarver w;
+    L.imp = w.take((size_t)T * 4);
+    L.remaining = w.take((size_t)C * 4);
+    L.mtrack = w.take((size_t)M * 4);
+    L.sel_off = w.take((size_t)T * 4);
+    L.total = w.o;
     return L;
 }
 
@@ -491,22 +439,20 @@ __global__ void ta_mfas_sum(MfasArgs a) {
     a.inlier[e] = a.use[e] && s / (double)a.n_dir < a.thr;
 }
 
-struct MfasLayout { size_t use, node_off, inc, hist, dup, viol, total; int n_chunks, chunk, words; };
+struct MfasLayout { size_t use, node_off, inc, hist, dup, viol, total; CsrChunks chunks; int words; };
 
 MfasLayout mfas_layout(long long E, int n, int n_dir) {
     MfasLayout L;
-    L.n_chunks = csr_chunks(E);
-    L.chunk = (int)((E + L.n_chunks - 1) / L.n_chunks);
+    L.chunks = csr_chunks(E, kChunksMax);
     L.words = (int)((E + 31) / 32);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += gtsfm_align_up(bytes, 256); return at; };
-    L.use = take((size_t)E);
-    L.node_off = take(((size_t)n + 1) * 4);
-    L.inc = take((size_t)E * 8);
-    L.hist = take((size_t)L.n_chunks * n * 4);
-    L.dup = take((size_t)n);
-    L.viol = take((size_t)n_dir * L.words * 4);
-    L.total = o;
+    WsCarver w;
+    L.use = w.take((size_t)E);
+    L.node_off = w.take(((size_t)n + 1) * 4);
+    L.inc = w.take((size_t)E * 8);
+    L.hist = w.take(csr_hist_bytes(L.chunks, n));
+    L.dup = w.take((size_t)n);
+    L.viol = w.take((size_t)n_dir * L.words * 4);
+    L.total = w.o;
     return L;
 }
 
@@ -552,47 +498,6 @@ struct RecArgs {
     const int* node_off;
     const int* inc;
 };
-
-__device__ __forceinline__ double huber_loss(double d) {
-    return d <= kHuberK ? 0.5 * d * d : kHuberK * d - 0.5 * kHuberK * kHuberK;
-}
-__device__ __forceinline__ double huber_weight(double d) { return d <= kHuberK ? 1.0 : kHuberK / d; }
-
-__device__ bool inv3(const double* A, double* I) {
-    const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
-    const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
-    if (!(fabs(det) > 0.0) || !isfinite(det)) return false;
-    const double id = 1.0 / det;
-    I[0] = c00 * id;
-    I[1] = (A[2] * A[7] - A[1] * A[8]) * id;
-    I[2] = (A[1] * A[5] - A[2] * A[4]) * id;
-    I[3] = c01 * id;
-    I[4] = (A[0] * A[8] - A[2] * A[6]) * id;
-    I[5] = (A[2] * A[3] - A[0] * A[5]) * id;
-    I[6] = c02 * id;
-    I[7] = (A[1] * A[6] - A[0] * A[7]) * id;
-    I[8] = (A[0] * A[4] - A[1] * A[3]) * id;
-    return true;
-}
-
-template <int NV>
-__device__ __forceinline__ void block_sum(double* v, double* sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    }
-    if (lane == 0)
-        for (int k = 0; k < NV; ++k) sh[wave * NV + k] = v[k];
-    __syncthreads();
-    for (int k = 0; k < NV; ++k) {
-        double s = sh[k];
-        for (int w = 1; w < nw; ++w) s += sh[w * NV + k];
-        v[k] = s;
-    }
-    __syncthreads();
-}
 
 __global__ void rec_init(RecArgs a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -997,39 +902,37 @@ __global__ void rec_stats(RecArgs a, double* stats, double err0, double err, dou
 struct RecLayout {
     size_t cam_inl, isvar, active, rep, rkey, ruse, icnt, XA, XB, lin, D, g, Minv, ye, te, tl, vec, scal, node_off, inc,
         hist, total;
-    int n_chunks, chunk;
+    CsrChunks chunks;
 };
 
 RecLayout rec_layout(long long E, int n_img, int n) {
     RecLayout L;
     const long long E1 = E + 1;
-    L.n_chunks = csr_chunks(E1);
-    L.chunk = (int)((E1 + L.n_chunks - 1) / L.n_chunks);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += gtsfm_align_up(bytes ? bytes : 1, 256); return at; };
+    L.chunks = csr_chunks(E1, kChunksMax);
+    WsCarver w;
     const size_t e = (size_t)E1, v = (size_t)n, d = sizeof(double);
-    L.cam_inl = take((size_t)n_img);
-    L.isvar = take(v);
-    L.active = take(v);
-    L.rep = take(v * 4);
-    L.rkey = take(e * 8);
-    L.ruse = take(e);
-    L.icnt = take(I_COUNT * 4);
-    L.XA = take(v * 3 * d);
-    L.XB = take(v * 3 * d);
-    L.lin = take(e * kLin * d);
-    L.D = take(v * 9 * d);
-    L.g = take(v * 3 * d);
-    L.Minv = take(v * 9 * d);
-    L.ye = take(e * 3 * d);
-    L.te = take(e * d);
-    L.tl = take(e * d);
-    L.vec = take(5 * 3 * v * d);
-    L.scal = take(S_COUNT * d);
-    L.node_off = take((v + 1) * 4);
-    L.inc = take(e * 8);
-    L.hist = take((size_t)L.n_chunks * v * 4);
-    L.total = o;
+    L.cam_inl = w.take((size_t)n_img);
+    L.isvar = w.take(v);
+    L.active = w.take(v);
+    L.rep = w.take(v * 4);
+    L.rkey = w.take(e * 8);
+    L.ruse = w.take(e);
+    L.icnt = w.take(I_COUNT * 4);
+    L.XA = w.take(v * 3 * d);
+    L.XB = w.take(v * 3 * d);
+    L.lin = w.take(e * kLin * d);
+    L.D = w.take(v * 9 * d);
+    L.g = w.take(v * 3 * d);
+    L.Minv = w.take(v * 9 * d);
+    L.ye = w.take(e * 3 * d);
+    L.te = w.take(e * d);
+    L.tl = w.take(e * d);
+    L.vec = w.take(5 * 3 * v * d);
+    L.scal = w.take(S_COUNT * d);
+    L.node_off = w.take((v + 1) * 4);
+    L.inc = w.take(e * 8);
+    L.hist = w.take(csr_hist_bytes(L.chunks, v));
+    L.total = w.o;
     return L;
 }
 
@@ -1118,8 +1021,8 @@ int gtsfm_transavg_mfas(const int* d_meas_key, const double* d_meas_dir, const u
     CsrArgs c;
     c.key = d_meas_key; c.use = use; c.E = E; c.n = n_nodes;
     c.node_off = (int*)(ws + L.node_off); c.inc = (int*)(ws + L.inc); c.hist = (int*)(ws + L.hist);
-    c.dup = ws + L.dup; c.n_chunks = L.n_chunks; c.chunk = L.chunk;
-    int rc = csr_build(c, stream);
+    c.dup = ws + L.dup; c.chunks = L.chunks;
+    int rc = ta_csr_build(c, stream);
     if (rc != GTSFM_OK) return rc;
     MfasArgs a;
     a.key = d_meas_key; a.dir = d_meas_dir; a.use = use; a.E = E; a.n = n_nodes; a.n_dir = n_dir; a.words = L.words;
@@ -1172,16 +1075,8 @@ int gtsfm_transavg_recover(const int* d_meas_key, const double* d_meas_dir, cons
                    g3 = blocks_for(n3, B);
     int icnt[I_COUNT];
     double scal[6];
-    auto read_icnt = [&]() -> int {
-        GTSFM_CHECK_HIP(hipMemcpyAsync(icnt, a.icnt, sizeof(icnt), hipMemcpyDeviceToHost, stream));
-        GTSFM_CHECK_HIP(hipStreamSynchronize(stream));
-        return GTSFM_OK;
-    };
-    auto read_scal = [&]() -> int {
-        GTSFM_CHECK_HIP(hipMemcpyAsync(scal, a.scal, sizeof(scal), hipMemcpyDeviceToHost, stream));
-        GTSFM_CHECK_HIP(hipStreamSynchronize(stream));
-        return GTSFM_OK;
-    };
+    auto read_icnt = [&]() { return read_back(icnt, a.icnt, I_COUNT, stream); };
+    auto read_scal = [&]() { return read_back(scal, a.scal, 6, stream); };
     const size_t nmax = (size_t)E + 1 > (size_t)n ? (size_t)E + 1 : (size_t)n;
     hipLaunchKernelGGL(rec_init, dim3(blocks_for(nmax, B)), dim3(B), 0, stream, a);
     hipLaunchKernelGGL(rec_caminl, dim3(gE), dim3(B), 0, stream, a);
@@ -1200,8 +1095,8 @@ int gtsfm_transavg_recover(const int* d_meas_key, const double* d_meas_dir, cons
         CsrArgs c;
         c.key = a.rkey; c.use = a.ruse; c.E = E + 1; c.n = n;
         c.node_off = (int*)(ws + L.node_off); c.inc = (int*)(ws + L.inc); c.hist = (int*)(ws + L.hist);
-        c.dup = nullptr; c.n_chunks = L.n_chunks; c.chunk = L.chunk;
-        if ((rc = csr_build(c, stream)) != GTSFM_OK) return rc;
+        c.dup = nullptr; c.chunks = L.chunks;
+        if ((rc = ta_csr_build(c, stream)) != GTSFM_OK) return rc;
         hipLaunchKernelGGL(rec_eval, dim3(gE), dim3(B), 0, stream, a, X);
         hipLaunchKernelGGL(rec_reduce, dim3(1), dim3(kVecBlock), 0, stream, a, X, X, 0);
         GTSFM_CHECK_HIP(hipGetLastError());
@@ -1225,55 +1120,36 @@ int gtsfm_transavg_recover(const int* d_meas_key, const double* d_meas_dir, cons
                     hipLaunchKernelGGL(rec_pcg_init, dim3(1), dim3(kVecBlock), 0, stream, a);
                     GTSFM_CHECK_HIP(hipGetLastError());
                     if ((rc = read_icnt()) != GTSFM_OK) return rc;
-                    bool success = false, stop = false;
-                    double newErr = INFINITY;
+                    LmTrial trial;
                     if (!icnt[I_BAD]) {
                         if ((rc = read_scal()) != GTSFM_OK) return rc;
-                        const double bb = scal[S_BB];
-                        double rr = scal[S_RR];
-                        int k = 0;
-                        while (isfinite(rr) && !(sqrt(rr) <= pcg_rel_tol * sqrt(bb))) {
-                            if (k >= pcg_max_iter) {
-                                ++cap_hits;
-                                break;
-                            }
+                        rc = pcg_iterate(scal[S_BB], scal[S_RR], pcg_rel_tol, pcg_max_iter, pcg_total, cap_hits,
+                                         [&](double& rr) -> int {
                             hipLaunchKernelGGL(rec_prod_edges, dim3(gE), dim3(B), 0, stream, a, a.p);
                             hipLaunchKernelGGL(rec_prod_nodes, dim3(gW), dim3(kNodeBlock), 0, stream, a, lambda);
                             hipLaunchKernelGGL(rec_pcg_step, dim3(1), dim3(kVecBlock), 0, stream, a);
                             GTSFM_CHECK_HIP(hipGetLastError());
-                            if ((rc = read_scal()) != GTSFM_OK) return rc;
+                            const int rc2 = read_scal();
                             rr = scal[S_RR];
-                            ++k;
-                        }
-                        pcg_total += k;
+                            return rc2;
+                        });
+                        if (rc != GTSFM_OK) return rc;
                         hipLaunchKernelGGL(rec_update, dim3(g3), dim3(B), 0, stream, a, X, Xn);
                         hipLaunchKernelGGL(rec_prod_edges, dim3(gE), dim3(B), 0, stream, a, a.x);
                         hipLaunchKernelGGL(rec_step_cost, dim3(gE), dim3(B), 0, stream, a, Xn);
                         hipLaunchKernelGGL(rec_reduce, dim3(1), dim3(kVecBlock), 0, stream, a, Xn, X, 1);
                         GTSFM_CHECK_HIP(hipGetLastError());
                         if ((rc = read_scal()) != GTSFM_OK) return rc;
-                        const double newLin = scal[S_NEWLIN], linChange = oldLin - newLin;
-                        if (linChange >= 0) {
-                            newErr = scal[S_NEWERR];
-                            const double costChange = err - newErr;
-                            if (linChange > kDblEps * oldLin) success = costChange / linChange > kMinFidelity;
-                            else success = true;
-                            if (fabs(costChange) < 1e-5 * err) stop = true;
-                        }
+                        trial = lm_judge(err, oldLin, scal[S_NEWLIN], scal[S_NEWERR]);
                     }
-                    if (success) {
+                    if (trial.success) {
                         double* s = X; X = Xn; Xn = s;
-                        err = newErr;
-                        lambda /= 10.0;
+                        err = trial.newErr;
                         ++iters;
-                        break;
                     }
-                    if (stop) break;
-                    lambda *= 10.0;
-                    if (lambda >= kLambdaUpper) break;
+                    if (lm_trials_done(trial, lambda)) break;
                 }
-                const double dec = cur - err;
-                if (iters >= max_iters || dec / cur <= 1e-5 || dec <= 1e-5 || !isfinite(cur)) break;
+                if (lm_done(cur, err, iters, max_iters)) break;
             }
         }
         if (!isfinite(err)) status = 2.0;

@@ -31,16 +31,15 @@
 
 #pragma clang fp contract(off)
 
+#include "lm.hpp"   // the LM constants
+#include "se3.hpp"  // chol3_solve
+
 namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
 
-constexpr double kMinFidelity = 1e-3;
-constexpr double kLambdaUpper = 1e5;
-constexpr double kDblEps = 2.220446049250313e-16;
 constexpr double kRankTol = 1e-9;
-constexpr int kInnerMax = 64;
 constexpr double kRadToDeg = 57.29577951308232;
 
 #define TG_BLOCK 128
@@ -188,32 +187,6 @@ __device__ __forceinline__ double tg_factor(const Cam& c, const double* p, const
                 Jp[3 * r + j] = D[3 * r] * c.R[3 * j] + D[3 * r + 1] * c.R[3 * j + 1] + D[3 * r + 2] * c.R[3 * j + 2];
     }
     return 0.5 * (e[0] * e[0] + e[1] * e[1]);
-}
-
-__device__ __forceinline__ bool tg_chol3_solve(double* a, double* b) {
-    for (int j = 0; j < 3; ++j) {
-        double s = a[4 * j];
-        for (int k = 0; k < j; ++k) s -= a[3 * j + k] * a[3 * j + k];
-        if (!(s > 0.0)) return false;
-        const double d = sqrt(s);
-        a[4 * j] = d;
-        for (int i = j + 1; i < 3; ++i) {
-            double v = a[3 * i + j];
-            for (int k = 0; k < j; ++k) v -= a[3 * i + k] * a[3 * j + k];
-            a[3 * i + j] = v / d;
-        }
-    }
-    for (int i = 0; i < 3; ++i) {
-        double v = b[i];
-        for (int k = 0; k < i; ++k) v -= a[3 * i + k] * b[k];
-        b[i] = v / a[4 * i];
-    }
-    for (int i = 2; i >= 0; --i) {
-        double v = b[i];
-        for (int k = i + 1; k < 3; ++k) v -= a[3 * k + i] * b[k];
-        b[i] = v / a[4 * i];
-    }
-    return true;
 }
 
 // The measurements a solve uses: the pair (ka, kb) when mask is null, else every k of the track with mask[k] set and a
@@ -383,7 +356,7 @@ __device__ __attribute__((noinline)) bool tg_triangulate(const TgArgs& a, const 
                 for (int i = 0; i < 3; ++i) Hd[4 * i] += lambda;
                 bool success = false, stop = false;
                 double newp[3], newErr = INFINITY;
-                if (tg_chol3_solve(Hd, d)) {
+                if (chol3_solve(Hd, d)) {
                     // linearised decrease of the undamped system at d: |e|^2 / 2 - |J d + e|^2 / 2 = d.g - d.H d / 2
                     double dHd = 0.0;
 #pragma unroll

@@ -30,6 +30,39 @@ def test_no_m0_clobbers_in_sources():
             assert not re.search(r':\s*"[^"]*"\s*,\s*"m0"|"m0"\s*\)', src), name
 
 
+# The helpers the back-end stages share (se3.hpp, reduce.hpp, csr.hpp, lm.hpp, common.hpp), by the text that opens
+# their definition. rotavg.hip keeps a scalar `double block_sum(double, ...)` of its own, an LDS tree with another
+# summation order, so block_sum is matched with its return type.
+SHARED_HELPERS = {name: rf"\b{name}\(" for name in (
+    "skew3", "mm3", "mtv3", "mv3", "so3_exp", "so3_log", "pose_retract", "pose_log", "project", "project_jac", "inv3",
+    "chol3_solve", "huber_loss", "huber_weight", "ld_int", "st_int", "uf_find", "uf_unite", "csr_hist", "csr_colscan",
+    "csr_scan", "csr_scatter", "csr_build", "csr_chunks", "blocks_for", "read_back", "lm_judge", "lm_trials_done",
+    "lm_done", "pcg_iterate")}
+SHARED_HELPERS.update({"Pose": r"struct Pose\b", "WsCarver": r"struct WsCarver\b", "kHuberK": r"\bkHuberK =",
+                       "block_sum": r"void block_sum\("})
+# front-end files that carve their workspace with a lambda of their own (an empty piece takes no bytes there)
+OWN_TAKE = {"fundamental.hip", "ransac.hip", "sift.hip", "superglue.hip"}
+
+
+def test_shared_helpers_are_defined_once():
+    """Each shared helper has one definition under gtsfm_amd/csrc, so that a fix cannot reach one copy only. A
+    definition starts at column 0 with a qualifier or a return type; calls are indented."""
+    defined = {name: [] for name in SHARED_HELPERS}
+    for fname in sorted(os.listdir(CSRC)):
+        if not fname.endswith((".hip", ".hpp")):
+            continue
+        src = open(os.path.join(CSRC, fname)).read()
+        assert fname in OWN_TAKE or not re.search(r"auto take\b", src), f"{fname}: use WsCarver (common.hpp)"
+        for line in src.splitlines():
+            if not line or line[0] in " \t/#}":
+                continue
+            for name, pat in SHARED_HELPERS.items():
+                if re.search(pat, line):
+                    defined[name].append(fname)
+    for name, files in defined.items():
+        assert len(files) == 1, f"{name} is defined in {files}: keep one definition in a shared header"
+
+
 @pytest.fixture(scope="module")
 def sift_isa(tmp_path_factory):
     if not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists("/opt/rocm/bin/hipcc")):
