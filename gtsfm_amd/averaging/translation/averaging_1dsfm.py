@@ -17,7 +17,7 @@ import torch
 
 from gtsfm_amd import device, native
 from gtsfm_amd.averaging.translation.translation_averaging_base import TranslationAveragingBase
-from gtsfm_amd.common import geometry
+from gtsfm_amd.common import geometry, upload
 from gtsfm_amd.common.sfm_track import SfmTrack2d
 
 MAX_PROJECTION_DIRECTIONS = 2000
@@ -115,7 +115,7 @@ class TranslationAveraging1DSFM(TranslationAveragingBase):
         if self._reject_outliers and counts[0] > 0:
             need_dirs = self._projection_sampling_method == self.ProjectionSamplingMethod.SAMPLE_INPUT_MEASUREMENTS
             proj = self.sample_projection_directions(dirs[valid.bool()] if need_dirs else None)
-            proj = torch.from_numpy(np.ascontiguousarray(proj)).to(key.device)
+            proj = upload.to_device(proj, key.device)
             osum, inlier, _ = device.transavg_mfas(key, dirs, valid, n_img + n_land, proj, self._outlier_weight_threshold)
         rec = device.transavg_recover(key, dirs, inlier, n_img, n_land, rot_valid, self._robust_measurement_noise,
                                       scale_factor, self._seed, 0, self._pcg_rel_tol, self._pcg_max_iter)
@@ -143,8 +143,7 @@ class TranslationAveraging1DSFM(TranslationAveragingBase):
         metrics["num_outlier_1dsfm_measurements"] = metrics["num_total_1dsfm_measurements"]
         if not pairs:
             return [None] * num_images, metrics
-        native.require_gpu()
-        dev = torch.device("cuda")
+        dev = upload.cuda_device()
         u = np.zeros((len(pairs), 3))
         ev = np.zeros(len(pairs), np.uint8)
         for k, p in enumerate(pairs):
@@ -158,7 +157,6 @@ class TranslationAveraging1DSFM(TranslationAveragingBase):
             if r is not None:
                 R[i] = geometry.rotation_matrix(r)
                 rv[i] = 1
-        put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         track_args = {}
         if use_tracks and len(tracks_2d) > 0:
             lens = [t.number_measurements() for t in tracks_2d]
@@ -170,9 +168,11 @@ class TranslationAveraging1DSFM(TranslationAveragingBase):
             for i, c in enumerate(intrinsics):
                 if c is not None:
                     K[i] = geometry.calibration_params(c)
-            track_args = dict(track_offsets=put(off), track_img=put(img), track_uv=put(uv), intrinsics=put(K))
-        res = self.run_translation_averaging_arrays(put(np.asarray(pairs, np.int32).reshape(-1, 2)), put(u), put(R),
-                                                    put(ev), put(rv), scale_factor=scale_factor, **track_args)
+            track_args = dict(track_offsets=off, track_img=img, track_uv=uv, intrinsics=K)
+        edges = np.asarray(pairs, np.int32).reshape(-1, 2)
+        res = self.run_translation_averaging_arrays(
+            *(upload.to_device(a, dev) for a in (edges, u, R, ev, rv)), scale_factor=scale_factor,
+            **{k: upload.to_device(a, dev) for k, a in track_args.items()})
         wti, ok = res.wti.cpu().numpy(), res.wti_valid.cpu().numpy()
         inl = int(res.inlier[: len(pairs)].sum().item())
         metrics["num_inlier_1dsfm_measurements"] = inl

@@ -18,15 +18,10 @@ import numpy as np
 import torch
 
 from gtsfm_amd import device, native
-from gtsfm_amd.common import geometry
+from gtsfm_amd.common import geometry, upload
 from gtsfm_amd.common.sfm_track import SfmTrack
 from gtsfm_amd.data_association.dsf_tracks_estimator import Tracks2d
 from gtsfm_amd.data_association.point3d_initializer import Triangulated, camera_arrays
-
-
-def _ba_device() -> torch.device:
-    """The device the host-API form stages its arrays on."""
-    return torch.device("cuda")
 
 
 class BaData(NamedTuple):
@@ -93,8 +88,7 @@ class BundleAdjustmentOptimizer:
         dev = tracks.offsets.device
         if isinstance(cameras, dict):
             c = camera_arrays(cameras)
-            cams = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                         for a in (c.wRc, c.wtc, c.intrinsics, c.valid))
+            cams = tuple(upload.to_device(a, dev) for a in (c.wRc, c.wtc, c.intrinsics, c.valid))
         else:
             cams = tuple(cameras)
         wRc, wtc, intr, cam_valid = cams
@@ -122,8 +116,7 @@ class BundleAdjustmentOptimizer:
         n = initial_data.number_tracks()
         if n == 0 or len(initial_data.get_valid_camera_indices()) == 0:
             return initial_data, initial_data, [False] * n, 0.0
-        native.require_gpu()
-        dev = _ba_device()
+        dev = upload.cuda_device()
         cams = camera_arrays(initial_data.cameras)
         lens = [t.numberMeasurements() for t in initial_data.tracks]
         offsets = np.zeros(n + 1, np.int32)
@@ -132,13 +125,10 @@ class BundleAdjustmentOptimizer:
         image = np.array([m[0] for m in meas], np.int32)
         uv = np.array([np.asarray(m[1], np.float64).reshape(2) for m in meas], np.float64).reshape(-1, 2)
         point = np.array([np.asarray(t.point3(), np.float64).reshape(3) for t in initial_data.tracks]).reshape(-1, 3)
-
-        def put(a):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
+        csr = (upload.to_device(a, dev) for a in (offsets, image, uv, point))
         r = device.global_ba(
-            put(offsets), put(image), put(uv), put(point), None, None, put(cams.wRc), put(cams.wtc),
-            put(cams.intrinsics), put(cams.valid), robust=self._robust_measurement_noise,
+            *csr, None, None, *(upload.to_device(a, dev) for a in (cams.wRc, cams.wtc, cams.intrinsics, cams.valid)),
+            robust=self._robust_measurement_noise,
             measurement_sigma=self._measurement_noise_sigma, cam_pose3_prior_sigma=self._cam_pose3_prior_noise_sigma,
             max_iterations=self._max_iterations or 0, pcg_rel_tol=self._pcg_rel_tol, pcg_max_iter=self._pcg_max_iter,
             reproj_error_thresh=float("inf") if reproj_error_thresh is None else float(reproj_error_thresh))

@@ -16,7 +16,8 @@ from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from gtsfm_amd import device, native
+from gtsfm_amd import device
+from gtsfm_amd.common import upload
 from gtsfm_amd.common.keypoints import Keypoints
 from gtsfm_amd.common.sfm_track import SfmMeasurement, SfmTrack2d
 from gtsfm_amd.data_association.tracks_estimator_base import TracksEstimatorBase
@@ -41,14 +42,6 @@ class Tracks2d(NamedTuple):
     stats: ArrayLike
 
 
-def _rows_as_int32(v_corr: ArrayLike) -> torch.Tensor:
-    """Keypoint indices as the int32 tensor the kernel reads as uint32 (compact_verified's own dtype is kept as is)."""
-    if isinstance(v_corr, torch.Tensor):
-        return v_corr if v_corr.dtype == torch.int32 else v_corr.to(torch.int32)
-    arr = np.ascontiguousarray(v_corr)
-    return torch.from_numpy(arr.view(np.int32) if arr.dtype == np.uint32 else arr.astype(np.int32))
-
-
 class DsfTracksEstimator(TracksEstimatorBase):
     """Estimates tracks with a disjoint-set forest built on the GPU."""
 
@@ -71,24 +64,19 @@ class DsfTracksEstimator(TracksEstimatorBase):
         The result is of the kind of `pairs`: numpy in gives numpy out, a torch tensor in gives torch tensors on that
         tensor's device (a CPU tensor is copied to the GPU and the results back, like numpy). With `pairs` on the GPU
         the only host synchronisation is the one read of `stats` that sizes the returned slices."""
-        native.require_gpu()
         is_tensor = isinstance(pairs, torch.Tensor)
-        dev = pairs.device if is_tensor and pairs.is_cuda else torch.device("cuda")
-
-        def put(a, dtype, shape):
-            return torch.as_tensor(a).to(device=dev, dtype=dtype).reshape(shape).contiguous()
-
-        pairs_d = put(pairs, torch.int32, (-1, 2))
+        dev = upload.cuda_device(pairs)
+        pairs_d = upload.to_device(pairs, dev, torch.int32, (-1, 2))
         P = pairs_d.shape[0]
-        offsets_d = put(offsets, torch.int32, (-1,))
+        offsets_d = upload.to_device(offsets, dev, torch.int32, (-1,))
         if offsets_d.numel() < P + 1:
             raise ValueError(f"offsets has {offsets_d.numel()} entries for {P} pairs")
-        v_corr_d = _rows_as_int32(v_corr).to(dev).reshape(-1, 2).contiguous()
-        kp_count_d = put(kp_count, torch.int32, (-1,))
-        valid_d = None
-        if valid is not None:
-            valid_d = (torch.as_tensor(valid).to(dev).reshape(P) != 0).to(torch.uint8).contiguous()
-        kp_xy_d = None if kp_xy is None else put(kp_xy, torch.float32, (kp_count_d.numel(), int(kmax), 2))
+        # keypoint indices: a uint32 array is taken as the int32 tensor the kernel reads as uint32
+        v_corr_d = upload.to_device(v_corr, dev, torch.int32, (-1, 2))
+        kp_count_d = upload.to_device(kp_count, dev, torch.int32, (-1,))
+        valid_d = None if valid is None else upload.mask_to_device(valid, dev, P)
+        kp_xy_d = None if kp_xy is None else upload.to_device(kp_xy, dev, torch.float32,
+                                                              (kp_count_d.numel(), int(kmax), 2))
         t_off, t_img, t_kp, t_uv, stats = device.tracks_from_matches(pairs_d, offsets_d, v_corr_d, kp_count_d, int(kmax),
                                                                      valid=valid_d, kp_xy=kp_xy_d)
         stats_h = stats.cpu()  # the one synchronisation: the counts size the slices below

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd import device, native
-from gtsfm_amd.common import geometry
+from gtsfm_amd.common import geometry, upload
 from gtsfm_amd.common.sfm_track import SfmTrack, SfmTrack2d
 from gtsfm_amd.data_association.dsf_tracks_estimator import Tracks2d
 from gtsfm_amd.frontend.triangulation_options import (  # noqa: F401  (re-exported, as the reference module has them)
@@ -84,8 +84,7 @@ class Point3dInitializer:
     def _device_cameras(self, dev: torch.device):
         if self._cams_dev is None or self._cams_dev[0].device != dev:
             c = self._cams
-            self._cams_dev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                                   for a in (c.wRc, c.wtc, c.intrinsics, c.valid))
+            self._cams_dev = tuple(upload.to_device(a, dev) for a in (c.wRc, c.wtc, c.intrinsics, c.valid))
         return self._cams_dev
 
     def _n_hyp(self) -> int:
@@ -101,20 +100,15 @@ class Point3dInitializer:
         copy and no synchronisation. track_id (T,) int32 keys the sampling hash (default: the track's index);
         n_tracks_dev makes the track count a device value (see device.triangulate_tracks). With want_hypotheses the
         device result (device.TriangulationResult, with n_hyp and hyp_pair) is returned as well."""
-        native.require_gpu()
+        dev = upload.cuda_device(tracks.offsets)
         if self.options.mode == TriangulationSamplingMode.RANSAC_SAMPLE_BIASED_BASELINE:
             raise NotImplementedError("RANSAC_SAMPLE_BIASED_BASELINE is not built on the MI355X path")
         is_tensor = isinstance(tracks.offsets, torch.Tensor)
-        dev = tracks.offsets.device if is_tensor and tracks.offsets.is_cuda else torch.device("cuda")
-
-        def put(a, dtype, shape):
-            return torch.as_tensor(a).to(device=dev, dtype=dtype).reshape(shape).contiguous()
-
-        offsets = put(tracks.offsets, torch.int32, (-1,))
-        image = put(tracks.image, torch.int32, (-1,))
+        offsets = upload.to_device(tracks.offsets, dev, torch.int32, (-1,))
+        image = upload.to_device(tracks.image, dev, torch.int32, (-1,))
         uv_src = torch.as_tensor(tracks.uv)
-        uv = put(uv_src, torch.float64 if uv_src.dtype == torch.float64 else torch.float32, (-1, 2))
-        tid = None if track_id is None else put(track_id, torch.int32, (-1,))
+        uv = upload.to_device(uv_src, dev, torch.float64 if uv_src.dtype == torch.float64 else torch.float32, (-1, 2))
+        tid = None if track_id is None else upload.to_device(track_id, dev, torch.int32, (-1,))
         wRc, wtc, intr, valid = self._device_cameras(dev)
         res = device.triangulate_tracks(offsets, image, uv, wRc, wtc, intr, valid, MODE_TO_NATIVE[self.options.mode],
                                         self.options.reproj_error_threshold, self.options.min_triangulation_angle,

@@ -7,20 +7,96 @@ match_pairs(stats=...)).
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from gtsfm_amd import native
 
+_F32, _F64, _I32, _I64, _U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _u64(seed: int) -> int:
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _flag(b) -> int:
+    return 1 if b else 0
+
+
+def _check(t: Optional[torch.Tensor], name: str, dtype: Union[torch.dtype, Tuple[torch.dtype, ...]],
+           numel: Optional[int] = None, shape: Optional[Sequence[Optional[int]]] = None,
+           min_numel: Optional[int] = None, optional: bool = False) -> None:
+    """Every wrapper's tensor check: `t` is a contiguous device tensor of `dtype` (one, or a tuple to choose from)
+    with `numel` elements (or at least `min_numel`) or of `shape` (None = any extent); None passes when `optional`.
+    Raises AssertionError naming the argument."""
+    if t is None and optional:
+        return
+    ok = t is not None and t.is_cuda and t.is_contiguous() and \
+        (t.dtype in dtype if isinstance(dtype, tuple) else t.dtype == dtype)
+    if ok and numel is not None:
+        ok = t.numel() == numel
+    if ok and min_numel is not None:
+        ok = t.numel() >= min_numel
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape))
+    if not ok:
+        want = "".join(f", {k} {v}" for k, v in (("numel", numel), ("numel >=", min_numel), ("shape", shape))
+                       if v is not None)
+        got = "None" if t is None else f"{t.dtype} {tuple(t.shape)} on {t.device}, strides {t.stride()}"
+        raise AssertionError(f"{name} must be a contiguous device tensor of {dtype}{want}; got {got}")
+
+
+def _check_cameras(wRc: torch.Tensor, wtc: torch.Tensor, intrinsics: torch.Tensor,
+                   cam_valid: Optional[torch.Tensor]) -> int:
+    """Checks per-image poses (wRc, wtc), intrinsics (f, u0, v0) and the optional valid bytes; returns n_img."""
+    n_img = intrinsics.numel() // 3
+    _check(wRc, "wRc", _F64, numel=9 * n_img)
+    _check(wtc, "wtc", _F64, numel=3 * n_img)
+    _check(intrinsics, "intrinsics", _F64, numel=3 * n_img)
+    _check(cam_valid, "cam_valid", _U8, numel=n_img, optional=True)
+    return n_img
+
+
+def _track_csr(track_offsets: Optional[torch.Tensor], track_img: Optional[torch.Tensor],
+               track_uv: Optional[torch.Tensor], n_tracks: Optional[int],
+               n_tracks_dev: Optional[torch.Tensor]) -> Tuple[int, int, int]:
+    """Checks a track CSR (track_offsets (>= T + 1,) int32, track_img (n_meas,) int32, track_uv (n_meas, 2) float32 or
+    float64, n_tracks_dev int64 or None) and returns (T, n_meas, uv_is_f64). T is n_tracks, or track_offsets.numel()
+    - 1 (0 for an empty track_offsets); no CSR at all (track_offsets None) is (0, 0, 0)."""
+    _check(n_tracks_dev, "n_tracks_dev", _I64, min_numel=1, optional=True)
+    if track_offsets is None:
+        return 0, 0, 0
+    _check(track_offsets, "track_offsets", _I32)
+    _check(track_img, "track_img", _I32)
+    n_meas = track_img.numel()
+    _check(track_uv, "track_uv", (_F32, _F64), numel=2 * n_meas)
+    T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
+    assert 0 <= T <= max(track_offsets.numel() - 1, 0), f"n_tracks {T} for {track_offsets.numel()} track_offsets"
+    return T, n_meas, _flag(track_uv.dtype == _F64)
+
+
 def _workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+def _take_workspace(need: int, device: torch.device, workspace: Optional[torch.Tensor],
+                    stream: Optional[torch.cuda.Stream], unsupported: Optional[str] = None) -> torch.Tensor:
+    """The workspace tensor to hand to the library: the caller's if it holds `need` bytes, else a fresh one (never
+    below 256 bytes), recorded on `stream` since the kernels may still read it after the wrapper returns. need == 0
+    is the library's word for a shape it does not take: with `unsupported` given it raises that as NativeError."""
+    if need == 0 and unsupported is not None:
+        raise native.NativeError(unsupported)
+    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, device)
+    if stream is not None:
+        ws.record_stream(stream)
+    return ws
 
 
 def match_pairs(desc: torch.Tensor, counts: torch.Tensor, pairs: torch.Tensor, ratio: Optional[float],
@@ -50,30 +126,27 @@ def match_pairs(desc: torch.Tensor, counts: torch.Tensor, pairs: torch.Tensor, r
         idx: (P, kmax, 2) int32 tensor holding uint32 keypoint indices, rows [0, count) valid per pair.
         count: (P,) int32.
     """
-    assert desc.is_cuda and desc.dtype == torch.float32 and desc.dim() == 3 and desc.is_contiguous()
-    assert counts.dtype == torch.int32 and pairs.dtype == torch.int32 and pairs.is_contiguous()
+    _check(desc, "desc", _F32, shape=(None, None, None))
+    _check(counts, "counts", _I32)
+    _check(pairs, "pairs", _I32)
     n_img, kmax, dim = desc.shape
     n_pairs = pairs.shape[0]
     L = native.lib()
     if out is not None:
         idx, cnt = out
-        assert idx.dtype == torch.int32 and idx.is_contiguous() and tuple(idx.shape) == (n_pairs, kmax, 2)
-        assert cnt.dtype == torch.int32 and cnt.is_contiguous() and tuple(cnt.shape) == (n_pairs,)
+        _check(idx, "out[0]", _I32, shape=(n_pairs, kmax, 2))
+        _check(cnt, "out[1]", _I32, shape=(n_pairs,))
         cnt.zero_()
     else:
         idx = torch.empty((max(n_pairs, 1), kmax, 2), dtype=torch.int32, device=desc.device)
         cnt = torch.zeros((max(n_pairs, 1),), dtype=torch.int32, device=desc.device)
     if n_pairs == 0:
         return idx[:0], cnt[:0]
-    ws_bytes = L.gtsfm_match_workspace_bytes(n_img, kmax, dim, n_pairs, mode)
-    ws = _workspace(ws_bytes, desc.device)
-    if stream is not None:
-        ws.record_stream(stream)  # the kernels may still read it after this function returns
-    if groups is not None:
-        assert groups.is_cuda and groups.dtype == torch.int32 and groups.dim() == 2 and groups.is_contiguous()
+    _check(groups, "groups", _I32, shape=(None, None), optional=True)
+    ws = _take_workspace(L.gtsfm_match_workspace_bytes(n_img, kmax, dim, n_pairs, mode), desc.device, None, stream)
     rc = L.gtsfm_match_batched_grouped(
         _ptr(desc), _ptr(counts), n_img, kmax, dim, _ptr(pairs), n_pairs,
-        _ptr(groups) if groups is not None else None, 0 if groups is None else groups.shape[0],
+        _ptr(groups), 0 if groups is None else groups.shape[0],
         0 if groups is None else groups.shape[1], -1.0 if ratio is None else float(ratio), mode, _ptr(ws),
         ws.numel(), _ptr(idx), _ptr(cnt), native.stream_handle(stream))
     native.check(rc, "gtsfm_match_batched_grouped")
@@ -156,14 +229,30 @@ def pair_groups(pairs: np.ndarray, group_size: int) -> np.ndarray:
     return out
 
 
+@dataclass(eq=False)
 class RansacResult:
     """Per-pair verifier outputs (device tensors): E, R (i2Ri1), t (i2ti1), n_inliers, status, n_hyp, mask, and
     n_models (candidate models scored; E path only, else None)."""
 
-    def __init__(self, E, R, t, n_inliers, status, n_hyp, mask, n_models=None):
-        self.E, self.R, self.t = E, R, t
-        self.n_inliers, self.status, self.n_hyp, self.mask = n_inliers, status, n_hyp, mask
-        self.n_models = n_models
+    E: torch.Tensor
+    R: torch.Tensor
+    t: torch.Tensor
+    n_inliers: torch.Tensor
+    status: torch.Tensor
+    n_hyp: torch.Tensor
+    mask: torch.Tensor
+    n_models: Optional[torch.Tensor] = None
+
+
+def _check_two_view(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: torch.Tensor, match_idx: torch.Tensor,
+                    match_count: torch.Tensor, pair_ids: Optional[torch.Tensor]) -> None:
+    """The verifiers' inputs: kp_xy (n_img, kmax, 2) float32, intrinsics float64, match_idx / match_count int32 and
+    the optional (P,) int32 sampler keys."""
+    _check(kp_xy, "kp_xy", _F32, shape=(None, None, None))
+    _check(intrinsics, "intrinsics", _F64)
+    _check(match_idx, "match_idx", _I32)
+    _check(match_count, "match_count", _I32)
+    _check(pair_ids, "pair_ids", _I32, numel=pairs.shape[0], optional=True)
 
 
 def ransac_essential(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: torch.Tensor, match_idx: torch.Tensor,
@@ -179,10 +268,7 @@ def ransac_essential(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: torch
         pairs: (P, 2) int32; match_idx: (P, mcap, 2) int32 (uint32 values); match_count: (P,) int32.
         pair_ids: optional (P,) int32 sampler keys (default pair_id_base + p).
     """
-    assert pair_ids is None or (pair_ids.dtype == torch.int32 and pair_ids.is_cuda and pair_ids.numel() == pairs.shape[0])
-    assert kp_xy.is_cuda and kp_xy.dtype == torch.float32 and kp_xy.dim() == 3 and kp_xy.is_contiguous()
-    assert intrinsics.dtype == torch.float64 and intrinsics.is_contiguous()
-    assert match_idx.dtype == torch.int32 and match_idx.is_contiguous() and match_count.dtype == torch.int32
+    _check_two_view(kp_xy, intrinsics, pairs, match_idx, match_count, pair_ids)
     n_img, kmax, _ = kp_xy.shape
     P = pairs.shape[0]
     mcap = match_idx.shape[1]
@@ -197,9 +283,7 @@ def ransac_essential(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: torch
     n_inl, status, n_hyp, n_models = (i32[j * P1:(j + 1) * P1] for j in range(4))
     mask = torch.zeros((P1, max(mcap, 1)), dtype=torch.uint8, device=dev)
     if P > 0:
-        ws = _workspace(L.gtsfm_ransac_workspace_bytes(P, mcap), dev)
-        if stream is not None:
-            ws.record_stream(stream)
+        ws = _take_workspace(L.gtsfm_ransac_workspace_bytes(P, mcap), dev, None, stream)
         rc = L.gtsfm_ransac_E_batched(_ptr(kp_xy), _ptr(intrinsics), n_img, kmax, _ptr(pairs), P, _ptr(match_idx),
                                       _ptr(match_count), mcap, float(thr_px), float(prob), int(max_iters), int(scoring),
                                       int(seed),
@@ -222,9 +306,9 @@ def compact_verified(match_idx: torch.Tensor, match_count: torch.Tensor, res: "R
     Returns offsets (P + 1,) int32, v_corr (capacity, 2) int32 holding uint32 indices (rows offsets[p] ..
     offsets[p + 1] belong to pair p, matcher order), isp_ok (P,) uint8.
     """
-    assert match_idx.dtype == torch.int32 and match_idx.is_contiguous() and match_idx.dim() == 3
+    _check(match_idx, "match_idx", _I32, shape=(None, None, None))
     P, mcap = match_idx.shape[0], match_idx.shape[1]
-    assert res.mask.shape[0] == P and (P == 0 or res.mask.shape[1] == mcap) and res.mask.is_contiguous()
+    _check(res.mask, "res.mask", _U8, shape=(P, mcap if P else None))
     dev = match_idx.device
     offsets = out_offsets if out_offsets is not None else torch.empty(P + 1, dtype=torch.int32, device=dev)
     v_corr = out_v_corr if out_v_corr is not None else torch.empty((max(capacity, 1), 2), dtype=torch.int32, device=dev)
@@ -239,14 +323,19 @@ def compact_verified(match_idx: torch.Tensor, match_count: torch.Tensor, res: "R
     return offsets, v_corr, isp_ok
 
 
+@dataclass(eq=False)
 class BA2Result:
     """Post-BA per-pair outputs (device tensors): R (i2Ri1), t (unit i2ti1), mask (P, mcap) over the putatives,
     n_inliers (its row count), ba_status (0 ok, 1 no track, 2 none valid, 3 not run), iters, and `status` = the
     verifier's status (what the reference's R is None / not None follows)."""
 
-    def __init__(self, R, t, mask, n_inliers, ba_status, iters, status):
-        self.R, self.t, self.mask, self.n_inliers = R, t, mask, n_inliers
-        self.ba_status, self.iters, self.status = ba_status, iters, status
+    R: torch.Tensor
+    t: torch.Tensor
+    mask: torch.Tensor
+    n_inliers: torch.Tensor
+    ba_status: torch.Tensor
+    iters: torch.Tensor
+    status: torch.Tensor
 
 
 def bundle_adjust_2view(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: torch.Tensor, match_idx: torch.Tensor,
@@ -257,15 +346,14 @@ def bundle_adjust_2view(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: to
     """Two-view triangulation + bundle adjustment of every verified pair (gtsfm_ba2_batched) on the verifier's
     outputs `res` (same tensors as ransac_essential took). prior_Rt (P, 12) float64 (i2Ti1 R row-major, t) and
     prior_sigmas (P, 6) float64: optional relative-pose priors (a row with sigma[0] <= 0 has none)."""
-    assert kp_xy.is_cuda and kp_xy.dtype == torch.float32 and kp_xy.is_contiguous()
-    assert intrinsics.dtype == torch.float64 and match_idx.dtype == torch.int32 and match_idx.is_contiguous()
-    assert (prior_Rt is None) == (prior_sigmas is None)
-    if prior_Rt is not None:
-        assert prior_Rt.dtype == torch.float64 and prior_Rt.is_contiguous() and prior_Rt.is_cuda
-        assert prior_sigmas.dtype == torch.float64 and prior_sigmas.is_contiguous() and prior_sigmas.is_cuda
-        assert tuple(prior_Rt.shape) == (match_idx.shape[0], 12) and tuple(prior_sigmas.shape) == (match_idx.shape[0], 6)
+    _check(kp_xy, "kp_xy", _F32)
+    _check(intrinsics, "intrinsics", _F64)
+    _check(match_idx, "match_idx", _I32)
     n_img, kmax = kp_xy.shape[0], kp_xy.shape[1]
     P, mcap = match_idx.shape[0], match_idx.shape[1]
+    assert (prior_Rt is None) == (prior_sigmas is None), "prior_Rt and prior_sigmas come together"
+    _check(prior_Rt, "prior_Rt", _F64, shape=(P, 12), optional=True)
+    _check(prior_sigmas, "prior_sigmas", _F64, shape=(P, 6), optional=True)
     dev = kp_xy.device
     L = native.lib()
     R = torch.zeros((max(P, 1), 3, 3), dtype=torch.float64, device=dev)
@@ -275,9 +363,7 @@ def bundle_adjust_2view(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: to
     st = torch.zeros_like(n_out)
     iters = torch.zeros_like(n_out)
     if P > 0:
-        ws = _workspace(L.gtsfm_ba2_workspace_bytes(P, mcap), dev)
-        if stream is not None:
-            ws.record_stream(stream)
+        ws = _take_workspace(L.gtsfm_ba2_workspace_bytes(P, mcap), dev, None, stream)
         rc = L.gtsfm_ba2_batched(_ptr(kp_xy), _ptr(intrinsics), n_img, kmax, _ptr(pairs), P, _ptr(match_idx),
                                  _ptr(match_count), mcap, _ptr(res.mask), _ptr(res.R.contiguous()),
                                  _ptr(res.t.contiguous()), _ptr(res.status), _ptr(prior_Rt), _ptr(prior_sigmas),
@@ -294,9 +380,11 @@ def sampson_sq(F: torch.Tensor, row_pair: torch.Tensor, x1: torch.Tensor, x2: to
 
     F: (n_mats, 3, 3) float64; row_pair: (N,) int32; x1, x2: (N, 2) float64. Returns (N,) float64.
     """
-    assert F.dtype == torch.float64 and F.is_contiguous() and F.is_cuda
-    assert x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.is_contiguous() and x2.is_contiguous()
-    assert row_pair.dtype == torch.int32 and row_pair.numel() == x1.shape[0] == x2.shape[0]
+    _check(F, "F", _F64)
+    _check(x1, "x1", _F64)
+    _check(x2, "x2", _F64)
+    assert x1.shape[0] == x2.shape[0], "x1 and x2 have one row each per measurement"
+    _check(row_pair, "row_pair", _I32, numel=x1.shape[0])
     out = torch.empty(max(x1.shape[0], 1), dtype=torch.float64, device=F.device)
     rc = native.lib().gtsfm_sampson_sq_batched(_ptr(F), F.shape[0], _ptr(row_pair), _ptr(x1), _ptr(x2), x1.shape[0],
                                                int(precision), _ptr(out), native.stream_handle(stream))
@@ -321,10 +409,7 @@ def ransac_fundamental(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: tor
 
     Same tensor conventions as ransac_essential; thr_px is in pixels (no focal-length scaling).
     """
-    assert kp_xy.is_cuda and kp_xy.dtype == torch.float32 and kp_xy.dim() == 3 and kp_xy.is_contiguous()
-    assert intrinsics.dtype == torch.float64 and intrinsics.is_contiguous()
-    assert match_idx.dtype == torch.int32 and match_idx.is_contiguous() and match_count.dtype == torch.int32
-    assert pair_ids is None or (pair_ids.dtype == torch.int32 and pair_ids.is_cuda and pair_ids.numel() == pairs.shape[0])
+    _check_two_view(kp_xy, intrinsics, pairs, match_idx, match_count, pair_ids)
     n_img, kmax, _ = kp_xy.shape
     P = pairs.shape[0]
     mcap = match_idx.shape[1]
@@ -337,9 +422,7 @@ def ransac_fundamental(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: tor
     status, n_hyp = torch.zeros_like(n_inl), torch.zeros_like(n_inl)
     mask = torch.zeros((max(P, 1), max(mcap, 1)), dtype=torch.uint8, device=dev)
     if P > 0:
-        ws = _workspace(L.gtsfm_ransac_F_workspace_bytes(P, mcap), dev)
-        if stream is not None:
-            ws.record_stream(stream)
+        ws = _take_workspace(L.gtsfm_ransac_F_workspace_bytes(P, mcap), dev, None, stream)
         rc = L.gtsfm_ransac_F_batched(_ptr(kp_xy), _ptr(intrinsics), n_img, kmax, _ptr(pairs), P, _ptr(match_idx),
                                       _ptr(match_count), mcap, float(thr_px), float(prob), int(max_iters), int(seed),
                                       int(pair_id_base), _ptr(pair_ids), _ptr(ws), ws.numel(), _ptr(F), _ptr(E),
@@ -349,12 +432,16 @@ def ransac_fundamental(kp_xy: torch.Tensor, intrinsics: torch.Tensor, pairs: tor
     return FundamentalResult(F[:P], E[:P], R[:P], t[:P], n_inl[:P], status[:P], n_hyp[:P], mask[:P])
 
 
+@dataclass(eq=False)
 class SiftResult:
     """Per-image SIFT outputs (device tensors): xy (n,k,2), attr (n,k,3) size/angle/response, desc (n,k,128),
     count (n,), n_detected (n,)."""
 
-    def __init__(self, xy, attr, desc, count, n_detected):
-        self.xy, self.attr, self.desc, self.count, self.n_detected = xy, attr, desc, count, n_detected
+    xy: torch.Tensor
+    attr: torch.Tensor
+    desc: torch.Tensor
+    count: torch.Tensor
+    n_detected: torch.Tensor
 
 
 def sift_extract(images: torch.Tensor, max_kpts: int, stream: Optional[torch.cuda.Stream] = None,
@@ -362,9 +449,8 @@ def sift_extract(images: torch.Tensor, max_kpts: int, stream: Optional[torch.cud
                  masks: Optional[torch.Tensor] = None) -> SiftResult:
     """SIFT + top-k on a batch of same-sized uint8 images (n, H, W) gray or (n, H, W, 3) RGB (gtsfm_sift_batched).
     masks: optional (n, H, W) uint8; keypoints on zero pixels are dropped before the top-k."""
-    assert images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous()
-    assert masks is None or (masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()
-                             and tuple(masks.shape) == tuple(images.shape[:3]))
+    _check(images, "images", _U8)
+    _check(masks, "masks", _U8, shape=tuple(images.shape[:3]), optional=True)
     n = images.shape[0]
     H, W = images.shape[1], images.shape[2]
     C = 1 if images.dim() == 3 else images.shape[3]
@@ -376,10 +462,7 @@ def sift_extract(images: torch.Tensor, max_kpts: int, stream: Optional[torch.cud
                          torch.empty((n, max_kpts, 128), dtype=torch.float32, device=dev),
                          torch.empty((n,), dtype=torch.int32, device=dev),
                          torch.empty((n,), dtype=torch.int32, device=dev))
-    nbytes = L.gtsfm_sift_workspace_bytes(n, H, W, max_kpts)
-    ws = workspace if workspace is not None and workspace.numel() >= nbytes else _workspace(nbytes, dev)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_sift_workspace_bytes(n, H, W, max_kpts), dev, workspace, stream)
     rc = L.gtsfm_sift_batched(_ptr(images), _ptr(masks), n, H, W, C, max_kpts, _ptr(ws), ws.numel(), _ptr(out.xy),
                               _ptr(out.attr),
                               _ptr(out.desc), _ptr(out.count), _ptr(out.n_detected), native.stream_handle(stream))
@@ -387,12 +470,16 @@ def sift_extract(images: torch.Tensor, max_kpts: int, stream: Optional[torch.cud
     return out
 
 
+@dataclass(eq=False)
 class SuperPointResult:
     """Per-image SuperPoint outputs (device tensors): xy (n,k,2) float32 (x, y), scores (n,k), desc (n,k,256),
     count (n,), n_detected (n,)."""
 
-    def __init__(self, xy, scores, desc, count, n_detected):
-        self.xy, self.scores, self.desc, self.count, self.n_detected = xy, scores, desc, count, n_detected
+    xy: torch.Tensor
+    scores: torch.Tensor
+    desc: torch.Tensor
+    count: torch.Tensor
+    n_detected: torch.Tensor
 
 
 def superpoint_extract(images: torch.Tensor, weights: torch.Tensor, max_kpts: int, keypoint_threshold: float = 0.005,
@@ -408,10 +495,9 @@ def superpoint_extract(images: torch.Tensor, weights: torch.Tensor, max_kpts: in
     masks: optional (n, H, W) uint8 device tensor; a detection at (x, y) is kept iff masks[i, y, x] == 1 (the
     reference's Keypoints.filter_by_mask), before the top-k.
     """
-    assert images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous()
-    assert weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous()
+    _check(images, "images", _U8)
     L = native.lib()
-    assert weights.numel() == L.gtsfm_superpoint_weights_floats()
+    _check(weights, "weights", _F32, numel=L.gtsfm_superpoint_weights_floats())
     n, H, W = images.shape[0], images.shape[1], images.shape[2]
     C = 1 if images.dim() == 3 else images.shape[3]
     dev = images.device
@@ -421,18 +507,14 @@ def superpoint_extract(images: torch.Tensor, weights: torch.Tensor, max_kpts: in
                                torch.empty((n, max_kpts, 256), dtype=torch.float32, device=dev),
                                torch.zeros((n,), dtype=torch.int32, device=dev),
                                torch.zeros((n,), dtype=torch.int32, device=dev))
-    for t, shape in ((out.xy, (n, max_kpts, 2)), (out.scores, (n, max_kpts)), (out.desc, (n, max_kpts, 256))):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+    _check(out.xy, "out.xy", _F32, shape=(n, max_kpts, 2))
+    _check(out.scores, "out.scores", _F32, shape=(n, max_kpts))
+    _check(out.desc, "out.desc", _F32, shape=(n, max_kpts, 256))
     if n == 0:
         return out
-    need = L.gtsfm_superpoint_workspace_bytes(n, H, W, max_kpts)
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
-    if masks is not None:
-        assert masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()
-        assert tuple(masks.shape) == (n, H, W), (tuple(masks.shape), (n, H, W))
-    rc = L.gtsfm_superpoint_batched(_ptr(images), _ptr(masks) if masks is not None else None, n, H, W, C,
+    _check(masks, "masks", _U8, shape=(n, H, W), optional=True)
+    ws = _take_workspace(L.gtsfm_superpoint_workspace_bytes(n, H, W, max_kpts), dev, workspace, stream)
+    rc = L.gtsfm_superpoint_batched(_ptr(images), _ptr(masks), n, H, W, C,
                                     _ptr(weights), max_kpts, float(keypoint_threshold),
                                     int(nms_radius), int(remove_borders), _ptr(ws), ws.numel(), _ptr(out.xy),
                                     _ptr(out.scores), _ptr(out.desc), _ptr(out.count), _ptr(out.n_detected),
@@ -452,23 +534,22 @@ def superglue_match(kp: torch.Tensor, scores: torch.Tensor, desc: torch.Tensor, 
     image_hw (n_img, 2) int32 (H, W), pairs (P, 2) int32, weights: the packed blob. kmax must be a multiple of 64.
     Returns idx (P, kmax, 2) int32 (uint32 values, i ascending), count (P,) int32, mscores0 (P, kmax) f32.
     """
-    for t in (kp, scores, desc, weights):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-    assert counts.dtype == torch.int32 and image_hw.dtype == torch.int32 and pairs.dtype == torch.int32
+    _check(kp, "kp", _F32)
     n_img, kmax = kp.shape[0], kp.shape[1]
-    assert kmax % 64 == 0 and desc.shape == (n_img, kmax, 256) and scores.shape == (n_img, kmax)
+    assert kmax % 64 == 0, f"kmax {kmax} is no multiple of 64"
+    _check(scores, "scores", _F32, shape=(n_img, kmax))
+    _check(desc, "desc", _F32, shape=(n_img, kmax, 256))
+    for t, name in ((counts, "counts"), (image_hw, "image_hw"), (pairs, "pairs")):
+        _check(t, name, _I32)
     L = native.lib()
-    assert weights.numel() == L.gtsfm_superglue_weights_floats(n_layers)
+    _check(weights, "weights", _F32, numel=L.gtsfm_superglue_weights_floats(n_layers))
     P = pairs.shape[0]
     dev = kp.device
     idx = torch.zeros((max(P, 1), kmax, 2), dtype=torch.int32, device=dev)
     cnt = torch.zeros((max(P, 1),), dtype=torch.int32, device=dev)
     ms = torch.zeros((max(P, 1), kmax), dtype=torch.float32, device=dev)
     if P > 0:
-        need = L.gtsfm_superglue_workspace_bytes(P, kmax)
-        ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-        if stream is not None:
-            ws.record_stream(stream)
+        ws = _take_workspace(L.gtsfm_superglue_workspace_bytes(P, kmax), dev, workspace, stream)
         rc = L.gtsfm_superglue_batched(_ptr(kp), _ptr(scores), _ptr(desc), _ptr(counts), _ptr(image_hw), n_img, kmax,
                                        _ptr(pairs), P, _ptr(weights), int(n_layers), int(sinkhorn_iters),
                                        float(match_threshold), _ptr(ws), ws.numel(), _ptr(idx), _ptr(cnt), _ptr(ms),
@@ -532,7 +613,7 @@ def retrieval_pairs(scores: torch.Tensor, num_select: int, min_score: Optional[f
         return out, cnt
     use_min = min_score is not None
     native.check(native.lib().gtsfm_retrieval_pairs(_ptr(scores), n1, n2, _ptr(inv), int(num_select),
-                                                    float(min_score) if use_min else 0.0, int(use_min), _ptr(out),
+                                                    float(min_score) if use_min else 0.0, _flag(use_min), _ptr(out),
                                                     _ptr(cnt), native.stream_handle(stream)),
                  "gtsfm_retrieval_pairs")
     return out, cnt
@@ -546,22 +627,18 @@ def netvlad_describe(images: torch.Tensor, weights: torch.Tensor, whiten: bool =
     weights: the packed fp32 blob (gtsfm_amd.frontend.global_descriptor.netvlad_global_descriptor.pack_netvlad_weights).
     Returns (desc (n, 4096) f32 or None when whiten is False, vlad (n, 32768) f32 or None unless keep_vlad or
     not whiten): the whitened, L2-normalised descriptor and the NetVLADLayer output before whitening."""
-    assert images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4
+    _check(images, "images", _U8, shape=(None, None, None, None))
     assert images.shape[3] == 3, "NetVLAD takes RGB images (netvlad.py:172: image.shape[1] == 3)"
-    assert weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous()
     L = native.lib()
-    assert weights.numel() == L.gtsfm_netvlad_weights_floats()
+    _check(weights, "weights", _F32, numel=L.gtsfm_netvlad_weights_floats())
     n, H, W = images.shape[0], images.shape[1], images.shape[2]
     dev = images.device
     desc = torch.empty((n, 4096), dtype=torch.float32, device=dev) if whiten else None
     vlad = torch.empty((n, 32768), dtype=torch.float32, device=dev) if (keep_vlad or not whiten) else None
     if n == 0:
         return desc, vlad
-    need = L.gtsfm_netvlad_workspace_bytes(n, H, W)
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
-    rc = L.gtsfm_netvlad_batched(_ptr(images), n, H, W, 3, _ptr(weights), int(bool(whiten)), _ptr(vlad), _ptr(desc),
+    ws = _take_workspace(L.gtsfm_netvlad_workspace_bytes(n, H, W), dev, workspace, stream)
+    rc = L.gtsfm_netvlad_batched(_ptr(images), n, H, W, 3, _ptr(weights), _flag(whiten), _ptr(vlad), _ptr(desc),
                                  _ptr(ws), ws.numel(), native.stream_handle(stream))
     native.check(rc, "gtsfm_netvlad_batched")
     return desc, vlad
@@ -576,24 +653,18 @@ def viewgraph_cycle_filter(edges: torch.Tensor, R: torch.Tensor, valid: Optional
     edges: (E, 2) int32 (i1 < i2 < n_img, each pair once); R: (E, 3, 3) float64 i2Ri1; valid: (E,) uint8 or None.
     Returns (keep (E,) uint8, agg_error_deg (E,) float64, n_triplets (E,) int32, total_triplets (1,) int64 or None),
     all on the device and in input order."""
-    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous()
+    _check(edges, "edges", _I32, shape=(None, 2))
     E = edges.shape[0]
-    assert tuple(edges.shape) == (E, 2)
-    assert R.is_cuda and R.dtype == torch.float64 and R.is_contiguous() and R.numel() == 9 * E
-    if valid is not None:
-        assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == E
+    _check(R, "R", _F64, numel=9 * E)
+    _check(valid, "valid", _U8, numel=E, optional=True)
     dev = edges.device
     agg = torch.empty(E, dtype=torch.float64, device=dev)
     n_trip = torch.empty(E, dtype=torch.int32, device=dev)
     keep = torch.empty(E, dtype=torch.uint8, device=dev)
     total = torch.zeros(1, dtype=torch.int64, device=dev) if want_total else None
     L = native.lib()
-    need = L.gtsfm_viewgraph_workspace_bytes(int(n_img), E)
-    if E > 0 and need == 0:
-        raise native.NativeError(f"gtsfm_viewgraph_cycle_filter supports 1..{native.VG_MAX_IMAGES} images, got {n_img}")
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_viewgraph_workspace_bytes(int(n_img), E), dev, workspace, stream, None if E == 0 else
+                         f"gtsfm_viewgraph_cycle_filter supports 1..{native.VG_MAX_IMAGES} images, got {n_img}")
     rc = L.gtsfm_viewgraph_cycle_filter(_ptr(edges), _ptr(R), _ptr(valid), int(n_img), E, int(criterion),
                                         float(error_threshold_deg), _ptr(ws), ws.numel(), _ptr(agg), _ptr(n_trip),
                                         _ptr(keep), _ptr(total), native.stream_handle(stream))
@@ -618,19 +689,14 @@ def tracks_from_matches(pairs: torch.Tensor, offsets: torch.Tensor, v_corr: torc
     (meas_cap, 2) float32 or None, stats (5,) int64 = n_tracks, n_measurements, n_components, n_erroneous, n_bad_rows),
     all on the device; entries past the counts in stats are not written. Tracks are in canonical order: ascending
     smallest (image, keypoint), measurements ascending inside a track."""
-    assert pairs.is_cuda and pairs.dtype == torch.int32 and pairs.is_contiguous()
+    _check(pairs, "pairs", _I32, shape=(None, 2))
     P = pairs.shape[0]
-    assert tuple(pairs.shape) == (P, 2)
-    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= P + 1
-    assert v_corr.is_cuda and v_corr.dtype == torch.int32 and v_corr.is_contiguous() and v_corr.dim() == 2
-    assert v_corr.shape[1] == 2
-    assert kp_count.is_cuda and kp_count.dtype == torch.int32 and kp_count.is_contiguous()
+    _check(offsets, "offsets", _I32, min_numel=P + 1)
+    _check(v_corr, "v_corr", _I32, shape=(None, 2))
+    _check(kp_count, "kp_count", _I32)
     n_img, kmax = kp_count.numel(), int(kmax)
-    if valid is not None:
-        assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == P
-    if kp_xy is not None:
-        assert kp_xy.is_cuda and kp_xy.dtype == torch.float32 and kp_xy.is_contiguous()
-        assert kp_xy.numel() == n_img * kmax * 2
+    _check(valid, "valid", _U8, numel=P, optional=True)
+    _check(kp_xy, "kp_xy", _F32, numel=n_img * kmax * 2, optional=True)
     n_rows = v_corr.shape[0] if n_rows is None else int(n_rows)
     assert 0 <= n_rows <= v_corr.shape[0]
     dev = pairs.device
@@ -648,12 +714,9 @@ def tracks_from_matches(pairs: torch.Tensor, offsets: torch.Tensor, v_corr: torc
         t_uv = torch.empty((meas_cap, 2), dtype=torch.float32, device=dev) if kp_xy is not None else None
     stats = torch.empty(5, dtype=torch.int64, device=dev)
     L = native.lib()
-    need = L.gtsfm_tracks_workspace_bytes(n_img, kmax, P, n_rows)
-    if P > 0 and n_rows > 0 and need == 0:
-        raise native.NativeError(f"gtsfm_tracks_from_matches needs 0 < n_img * kmax < 2^31, got {n_img} x {kmax}")
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_tracks_workspace_bytes(n_img, kmax, P, n_rows), dev, workspace, stream,
+                         None if P == 0 or n_rows == 0 else
+                         f"gtsfm_tracks_from_matches needs 0 < n_img * kmax < 2^31, got {n_img} x {kmax}")
     rc = L.gtsfm_tracks_from_matches(_ptr(pairs), _ptr(offsets), _ptr(v_corr), _ptr(valid), P, n_rows, _ptr(kp_count),
                                      _ptr(kp_xy), n_img, kmax, _ptr(ws), ws.numel(), _ptr(t_off), track_cap,
                                      _ptr(t_img), _ptr(t_kp), _ptr(t_uv), meas_cap, _ptr(stats),
@@ -662,14 +725,19 @@ def tracks_from_matches(pairs: torch.Tensor, offsets: torch.Tensor, v_corr: torc
     return t_off, t_img, t_kp, t_uv, stats
 
 
+@dataclass(eq=False)
 class TriangulationResult:
     """Per-track outputs of triangulate_tracks, all on the device: exit_code (T,) int32, point (T, 3) float64 (NaN
     where the final triangulation did not succeed), avg_err (T,) float64, inlier (n_meas,) uint8, stats (8,) int64 in
     the order of native.TRI_STATS_FIELDS, and, when asked for, n_hyp (T,) int32 and hyp_pair (hyp_cap,) int64."""
 
-    def __init__(self, exit_code, point, avg_err, inlier, stats, n_hyp=None, hyp_pair=None):
-        self.exit_code, self.point, self.avg_err, self.inlier, self.stats = exit_code, point, avg_err, inlier, stats
-        self.n_hyp, self.hyp_pair = n_hyp, hyp_pair
+    exit_code: torch.Tensor
+    point: torch.Tensor
+    avg_err: torch.Tensor
+    inlier: torch.Tensor
+    stats: torch.Tensor
+    n_hyp: Optional[torch.Tensor] = None
+    hyp_pair: Optional[torch.Tensor] = None
 
 
 def triangulate_tracks(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: torch.Tensor,
@@ -688,25 +756,11 @@ def triangulate_tracks(track_offsets: torch.Tensor, track_img: torch.Tensor, tra
     tracks_from_matches), makes n_tracks a capacity, so that the chain needs no host synchronisation. wRc (n_img, 3,
     3), wtc (n_img, 3), intrinsics (n_img, 3) float64, cam_valid (n_img,) uint8 or None. mode is a
     native.GTSFM_TRI_* value. workspace_bytes below the query's value forces more chunks (tests)."""
-    assert track_offsets.is_cuda and track_offsets.dtype == torch.int32 and track_offsets.is_contiguous()
-    assert track_img.is_cuda and track_img.dtype == torch.int32 and track_img.is_contiguous()
-    assert track_uv.is_cuda and track_uv.dtype in (torch.float32, torch.float64) and track_uv.is_contiguous()
-    n_meas = track_img.numel()
-    assert track_uv.numel() == 2 * n_meas
-    T = track_offsets.numel() - 1 if n_tracks is None else int(n_tracks)
-    assert 0 <= T < track_offsets.numel() or T == 0
-    for t in (wRc, wtc, intrinsics):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    n_img = intrinsics.numel() // 3
-    assert wRc.numel() == 9 * n_img and wtc.numel() == 3 * n_img and intrinsics.numel() == 3 * n_img
-    if cam_valid is not None:
-        assert cam_valid.is_cuda and cam_valid.dtype == torch.uint8 and cam_valid.is_contiguous()
-        assert cam_valid.numel() == n_img
-    if n_tracks_dev is not None:
-        assert n_tracks_dev.is_cuda and n_tracks_dev.dtype == torch.int64 and n_tracks_dev.numel() >= 1
-    if track_id is not None:
-        assert track_id.is_cuda and track_id.dtype == torch.int32 and track_id.is_contiguous()
-        assert track_id.numel() >= T
+    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
+    # unlike global_ba and transavg_measurements, an empty track_offsets is refused unless n_tracks says 0
+    assert n_tracks is not None or track_offsets.numel() > 0, "track_offsets is empty"
+    n_img = _check_cameras(wRc, wtc, intrinsics, cam_valid)
+    _check(track_id, "track_id", _I32, min_numel=T, optional=True)
     if mode == native.GTSFM_TRI_RANSAC_SAMPLE_BIASED_BASELINE:
         raise NotImplementedError("RANSAC_SAMPLE_BIASED_BASELINE (a weighted draw without replacement) is not built")
     n_hyp = min(int(n_hyp), 2 ** 31 - 1)
@@ -725,14 +779,11 @@ def triangulate_tracks(track_offsets: torch.Tensor, track_img: torch.Tensor, tra
     need = L.gtsfm_triangulate_workspace_bytes(T, n_meas, n_hyp)
     if workspace_bytes is not None:
         need = int(workspace_bytes)
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
-    rc = L.gtsfm_triangulate_tracks(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv),
-                                    1 if track_uv.dtype == torch.float64 else 0, _ptr(track_id), T,
+    ws = _take_workspace(need, dev, workspace, stream)
+    rc = L.gtsfm_triangulate_tracks(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, _ptr(track_id), T,
                                     _ptr(n_tracks_dev), n_meas, _ptr(wRc), _ptr(wtc), _ptr(intrinsics),
                                     _ptr(cam_valid), n_img, int(mode), float(reproj_error_threshold),
-                                    float(min_triangulation_angle), n_hyp, int(seed) & (2 ** 64 - 1), _ptr(ws),
+                                    float(min_triangulation_angle), n_hyp, _u64(seed), _ptr(ws),
                                     need if workspace_bytes is not None else ws.numel(), _ptr(exit_code), _ptr(point),
                                     _ptr(avg_err), _ptr(inlier), _ptr(stats), _ptr(t_n_hyp), _ptr(hyp_pair),
                                     0 if hyp_pair is None else hyp_cap, native.stream_handle(stream))
@@ -740,13 +791,17 @@ def triangulate_tracks(track_offsets: torch.Tensor, track_img: torch.Tensor, tra
     return TriangulationResult(exit_code, point, avg_err, inlier, stats, t_n_hyp, hyp_pair)
 
 
+@dataclass(eq=False)
 class GlobalBaResult:
     """Outputs of global_ba, all on the device: wRc (n_img, 3, 3), wtc (n_img, 3), point (T, 3) float64, track_keep
     (T,) and cam_keep (n_img,) uint8, stats (10,) float64 in the order of native.GBA_STATS_FIELDS."""
 
-    def __init__(self, wRc, wtc, point, track_keep, cam_keep, stats):
-        self.wRc, self.wtc, self.point = wRc, wtc, point
-        self.track_keep, self.cam_keep, self.stats = track_keep, cam_keep, stats
+    wRc: torch.Tensor
+    wtc: torch.Tensor
+    point: torch.Tensor
+    track_keep: torch.Tensor
+    cam_keep: torch.Tensor
+    stats: torch.Tensor
 
 
 def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: torch.Tensor, point: torch.Tensor,
@@ -763,28 +818,13 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
     (T,) uint8 or bool or None, meas_valid (n_meas,) uint8 or None (the triangulation's inlier bytes). The call runs
     its LM / PCG control flow on the host and synchronises the stream; only those control scalars reach the host.
     workspace_bytes below the query's value is passed as is (tests of the capacity error)."""
-    assert track_offsets.is_cuda and track_offsets.dtype == torch.int32 and track_offsets.is_contiguous()
-    assert track_img.is_cuda and track_img.dtype == torch.int32 and track_img.is_contiguous()
-    assert track_uv.is_cuda and track_uv.dtype in (torch.float32, torch.float64) and track_uv.is_contiguous()
-    n_meas = track_img.numel()
-    assert track_uv.numel() == 2 * n_meas
-    T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
-    assert 0 <= T < track_offsets.numel() or T == 0
-    assert point.is_cuda and point.dtype == torch.float64 and point.is_contiguous() and point.numel() >= 3 * T
-    for t in (wRc, wtc, intrinsics):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    n_img = intrinsics.numel() // 3
-    assert wRc.numel() == 9 * n_img and wtc.numel() == 3 * n_img and intrinsics.numel() == 3 * n_img
-    if track_valid is not None:
-        if track_valid.dtype == torch.bool:
-            track_valid = track_valid.to(torch.uint8)
-        assert track_valid.is_cuda and track_valid.dtype == torch.uint8 and track_valid.is_contiguous()
-        assert track_valid.numel() >= T
-    for m, n in ((meas_valid, n_meas), (cam_valid, n_img)):
-        if m is not None:
-            assert m.is_cuda and m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == n
-    if n_tracks_dev is not None:
-        assert n_tracks_dev.is_cuda and n_tracks_dev.dtype == torch.int64 and n_tracks_dev.numel() >= 1
+    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
+    _check(point, "point", _F64, min_numel=3 * T)
+    n_img = _check_cameras(wRc, wtc, intrinsics, cam_valid)
+    if track_valid is not None and track_valid.dtype == torch.bool:
+        track_valid = track_valid.to(torch.uint8)
+    _check(track_valid, "track_valid", _U8, min_numel=T, optional=True)
+    _check(meas_valid, "meas_valid", _U8, numel=n_meas, optional=True)
     dev = track_offsets.device
     wRc_out = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
     wtc_out = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
@@ -793,16 +833,12 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
     cam_keep = torch.empty(n_img, dtype=torch.uint8, device=dev)
     stats = torch.empty(10, dtype=torch.float64, device=dev)
     L = native.lib()
-    need = L.gtsfm_global_ba_workspace_bytes(T, n_meas, n_img)
-    if T > 0 and n_meas > 0 and n_img > 0 and need == 0:
-        raise native.NativeError(f"gtsfm_global_ba: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
-    rc = L.gtsfm_global_ba(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv),
-                           1 if track_uv.dtype == torch.float64 else 0, T, _ptr(n_tracks_dev), n_meas, _ptr(point),
-                           _ptr(track_valid), _ptr(meas_valid), _ptr(wRc), _ptr(wtc), _ptr(intrinsics),
-                           _ptr(cam_valid), n_img, 1 if robust else 0, float(measurement_sigma),
+    ws = _take_workspace(L.gtsfm_global_ba_workspace_bytes(T, n_meas, n_img), dev, workspace, stream,
+                         None if T == 0 or n_meas == 0 or n_img == 0 else
+                         f"gtsfm_global_ba: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
+    rc = L.gtsfm_global_ba(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T, _ptr(n_tracks_dev),
+                           n_meas, _ptr(point), _ptr(track_valid), _ptr(meas_valid), _ptr(wRc), _ptr(wtc),
+                           _ptr(intrinsics), _ptr(cam_valid), n_img, _flag(robust), float(measurement_sigma),
                            float(cam_pose3_prior_sigma), int(max_iterations), float(pcg_rel_tol), int(pcg_max_iter),
                            float(reproj_error_thresh), _ptr(ws),
                            ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(wRc_out),
@@ -812,14 +848,19 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
     return GlobalBaResult(wRc_out, wtc_out, point_out, track_keep, cam_keep, stats)
 
 
+@dataclass(eq=False)
 class TransAvgMeasurements:
     """Outputs of transavg_measurements, all on the device: key (n_edges + n_meas, 2) int32, dir (.., 3) float64, valid
     (..,) uint8, selected (n_tracks,) int32, cam_valid (n_img,) uint8, counts (4,) int64 = valid camera edges, track
     slots in use, selected tracks, track measurements in a camera without rotation."""
 
-    def __init__(self, key, dir, valid, selected, cam_valid, counts, n_edges):
-        self.key, self.dir, self.valid, self.selected = key, dir, valid, selected
-        self.cam_valid, self.counts, self.n_edges = cam_valid, counts, n_edges
+    key: torch.Tensor
+    dir: torch.Tensor
+    valid: torch.Tensor
+    selected: torch.Tensor
+    cam_valid: torch.Tensor
+    counts: torch.Tensor
+    n_edges: int
 
 
 def transavg_measurements(edges: torch.Tensor, i2Ui1: torch.Tensor, edge_valid: Optional[torch.Tensor],
@@ -832,30 +873,18 @@ def transavg_measurements(edges: torch.Tensor, i2Ui1: torch.Tensor, edge_valid: 
     """World-frame direction measurements and track selection of 1DSfM (gtsfm_transavg_measurements; semantics in
     include/gtsfm_hip.h). edges (E, 2) int32 = (i1, i2), i2Ui1 (E, 3) float64, wRi (n_img, 3, 3) float64, the valid
     masks uint8 or None; the track CSR as tracks_from_matches returns it (or None: camera edges only)."""
-    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous() and edges.dim() == 2
+    _check(edges, "edges", _I32, shape=(None, 2))
     E = edges.shape[0]
-    assert edges.shape[1] == 2 and E > 0
-    for t in (i2Ui1, wRi):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     n_img = wRi.numel() // 9
-    assert i2Ui1.numel() == 3 * E and wRi.numel() == 9 * n_img and n_img > 0
-    for m, n in ((edge_valid, E), (rot_valid, n_img)):
-        if m is not None:
-            assert m.is_cuda and m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == n
+    assert E > 0 and n_img > 0, f"{E} edges, {n_img} images"
+    _check(i2Ui1, "i2Ui1", _F64, numel=3 * E)
+    _check(wRi, "wRi", _F64, numel=9 * n_img)
+    _check(edge_valid, "edge_valid", _U8, numel=E, optional=True)
+    _check(rot_valid, "rot_valid", _U8, numel=n_img, optional=True)
     dev = edges.device
-    T = n_meas = 0
+    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
     if track_offsets is not None:
-        assert track_offsets.is_cuda and track_offsets.dtype == torch.int32 and track_offsets.is_contiguous()
-        assert track_img.is_cuda and track_img.dtype == torch.int32 and track_img.is_contiguous()
-        assert track_uv.is_cuda and track_uv.dtype in (torch.float32, torch.float64) and track_uv.is_contiguous()
-        assert intrinsics.is_cuda and intrinsics.dtype == torch.float64 and intrinsics.is_contiguous()
-        assert intrinsics.numel() == 3 * n_img
-        n_meas = track_img.numel()
-        assert track_uv.numel() == 2 * n_meas
-        T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
-        assert 0 <= T < track_offsets.numel() or T == 0
-    if n_tracks_dev is not None:
-        assert n_tracks_dev.is_cuda and n_tracks_dev.dtype == torch.int64 and n_tracks_dev.numel() >= 1
+        _check(intrinsics, "intrinsics", _F64, numel=3 * n_img)
     key = torch.empty((E + n_meas, 2), dtype=torch.int32, device=dev)
     dirs = torch.empty((E + n_meas, 3), dtype=torch.float64, device=dev)
     valid = torch.empty(E + n_meas, dtype=torch.uint8, device=dev)
@@ -863,15 +892,10 @@ def transavg_measurements(edges: torch.Tensor, i2Ui1: torch.Tensor, edge_valid: 
     cam_valid = torch.empty(n_img, dtype=torch.uint8, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
     L = native.lib()
-    need = L.gtsfm_transavg_measurements_workspace_bytes(E, T, n_meas, n_img)
-    if need == 0:
-        raise native.NativeError(f"gtsfm_transavg_measurements: unsupported shape {E} edges, {T} tracks, {n_img} images")
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_transavg_measurements_workspace_bytes(E, T, n_meas, n_img), dev, workspace, stream,
+                         f"gtsfm_transavg_measurements: unsupported shape {E} edges, {T} tracks, {n_img} images")
     rc = L.gtsfm_transavg_measurements(_ptr(edges), _ptr(i2Ui1), _ptr(edge_valid), E, _ptr(wRi), _ptr(rot_valid), n_img,
-                                       _ptr(track_offsets), _ptr(track_img), _ptr(track_uv),
-                                       1 if track_uv is not None and track_uv.dtype == torch.float64 else 0, T,
+                                       _ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T,
                                        _ptr(n_tracks_dev), n_meas, _ptr(intrinsics), int(measurements_per_camera),
                                        _ptr(ws), ws.numel(), _ptr(key), _ptr(dirs), _ptr(valid), _ptr(selected),
                                        _ptr(cam_valid), _ptr(counts), native.stream_handle(stream))
@@ -886,13 +910,12 @@ def transavg_mfas(key: torch.Tensor, dirs: torch.Tensor, valid: Optional[torch.T
     """MFAS outlier weights over every projection direction in one launch (gtsfm_transavg_mfas). key (n, 2) int32,
     dirs (n, 3) float64, valid (n,) uint8 or None, proj (n_dir, 3) float64. Returns (outlier_sum (n,) float64, inlier
     (n,) uint8, violated (n_dir, ceil(n / 32)) int32 holding the uint32 bit words, or None)."""
-    assert key.is_cuda and key.dtype == torch.int32 and key.is_contiguous() and key.dim() == 2 and key.shape[1] == 2
+    _check(key, "key", _I32, shape=(None, 2))
     n = key.shape[0]
-    assert dirs.is_cuda and dirs.dtype == torch.float64 and dirs.is_contiguous() and dirs.numel() == 3 * n
-    assert proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.dim() == 2
+    _check(dirs, "dirs", _F64, numel=3 * n)
+    _check(proj, "proj", _F64, shape=(None, None))
     n_dir = proj.shape[0]
-    if valid is not None:
-        assert valid.is_cuda and valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == n
+    _check(valid, "valid", _U8, numel=n, optional=True)
     if n_nodes > native.TA_MFAS_MAX_NODES:
         raise native.NativeError(f"gtsfm_transavg_mfas holds its node state in LDS: {n_nodes} nodes exceed "
                                  f"{native.TA_MFAS_MAX_NODES}")
@@ -901,26 +924,25 @@ def transavg_mfas(key: torch.Tensor, dirs: torch.Tensor, valid: Optional[torch.T
     inlier = torch.empty(n, dtype=torch.uint8, device=dev)
     viol = torch.empty((n_dir, (n + 31) // 32), dtype=torch.int32, device=dev) if want_violated else None
     L = native.lib()
-    need = L.gtsfm_transavg_mfas_workspace_bytes(n, int(n_nodes), n_dir)
-    if need == 0:
-        raise native.NativeError(f"gtsfm_transavg_mfas: unsupported shape {n} measurements, {n_nodes} nodes, {n_dir} "
-                                 "directions")
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_transavg_mfas_workspace_bytes(n, int(n_nodes), n_dir), dev, workspace, stream,
+                         f"gtsfm_transavg_mfas: unsupported shape {n} measurements, {n_nodes} nodes, {n_dir} "
+                         "directions")
     rc = L.gtsfm_transavg_mfas(_ptr(key), _ptr(dirs), _ptr(valid), n, int(n_nodes), _ptr(proj), n_dir, float(threshold),
                                _ptr(ws), ws.numel(), _ptr(osum), _ptr(inlier), _ptr(viol), native.stream_handle(stream))
     native.check(rc, "gtsfm_transavg_mfas")
     return osum, inlier, viol
 
 
+@dataclass(eq=False)
 class TransAvgResult:
     """Outputs of transavg_recover, all on the device: wti (n_img, 3) float64, wti_valid (n_img,) uint8, landmark
     (n_landmarks, 3), landmark_valid, stats (10,) float64 in the order of native.TA_STATS_FIELDS."""
 
-    def __init__(self, wti, wti_valid, landmark, landmark_valid, stats):
-        self.wti, self.wti_valid, self.landmark, self.landmark_valid, self.stats = (wti, wti_valid, landmark,
-                                                                                    landmark_valid, stats)
+    wti: torch.Tensor
+    wti_valid: torch.Tensor
+    landmark: torch.Tensor
+    landmark_valid: torch.Tensor
+    stats: torch.Tensor
 
 
 def transavg_recover(key: torch.Tensor, dirs: torch.Tensor, inlier: torch.Tensor, n_img: int, n_landmarks: int,
@@ -930,12 +952,11 @@ def transavg_recover(key: torch.Tensor, dirs: torch.Tensor, inlier: torch.Tensor
                      ) -> TransAvgResult:
     """Camera and landmark positions from the inlier direction measurements (gtsfm_transavg_recover). Runs its LM / PCG
     control flow on the host and synchronises the stream."""
-    assert key.is_cuda and key.dtype == torch.int32 and key.is_contiguous() and key.dim() == 2 and key.shape[1] == 2
+    _check(key, "key", _I32, shape=(None, 2))
     n = key.shape[0]
-    assert dirs.is_cuda and dirs.dtype == torch.float64 and dirs.is_contiguous() and dirs.numel() == 3 * n
-    assert inlier.is_cuda and inlier.dtype == torch.uint8 and inlier.is_contiguous() and inlier.numel() == n
-    if rot_valid is not None:
-        assert rot_valid.is_cuda and rot_valid.dtype == torch.uint8 and rot_valid.numel() == n_img
+    _check(dirs, "dirs", _F64, numel=3 * n)
+    _check(inlier, "inlier", _U8, numel=n)
+    _check(rot_valid, "rot_valid", _U8, numel=n_img, optional=True)
     dev = key.device
     wti = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
     wti_valid = torch.empty(n_img, dtype=torch.uint8, device=dev)
@@ -943,15 +964,11 @@ def transavg_recover(key: torch.Tensor, dirs: torch.Tensor, inlier: torch.Tensor
     land_valid = torch.empty(n_landmarks, dtype=torch.uint8, device=dev)
     stats = torch.empty(10, dtype=torch.float64, device=dev)
     L = native.lib()
-    need = L.gtsfm_transavg_recover_workspace_bytes(n, int(n_img), int(n_landmarks))
-    if need == 0:
-        raise native.NativeError(f"gtsfm_transavg_recover: unsupported shape {n} measurements, {n_img} images, "
-                                 f"{n_landmarks} landmarks")
-    ws = workspace if workspace is not None and workspace.numel() >= need else _workspace(need, dev)
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_transavg_recover_workspace_bytes(n, int(n_img), int(n_landmarks)), dev, workspace,
+                         stream, f"gtsfm_transavg_recover: unsupported shape {n} measurements, {n_img} images, "
+                         f"{n_landmarks} landmarks")
     rc = L.gtsfm_transavg_recover(_ptr(key), _ptr(dirs), _ptr(inlier), n, int(n_img), int(n_landmarks), _ptr(rot_valid),
-                                  1 if robust else 0, float(scale), int(seed) & (2 ** 64 - 1), int(max_iterations),
+                                  _flag(robust), float(scale), _u64(seed), int(max_iterations),
                                   float(pcg_rel_tol), int(pcg_max_iter), _ptr(ws), ws.numel(), _ptr(wti),
                                   _ptr(wti_valid), _ptr(land) if n_landmarks else None,
                                   _ptr(land_valid) if n_landmarks else None, _ptr(stats), native.stream_handle(stream))
@@ -959,12 +976,14 @@ def transavg_recover(key: torch.Tensor, dirs: torch.Tensor, inlier: torch.Tensor
     return TransAvgResult(wti, wti_valid, land, land_valid, stats)
 
 
+@dataclass(eq=False)
 class RotAvgResult:
     """Outputs of rotavg_shonan, all on the device: wRi (n_img, 3, 3) float64 (zero where invalid), rot_valid (n_img,)
     uint8, stats (12,) float64 in the order of native.RA_STATS_FIELDS."""
 
-    def __init__(self, wRi, rot_valid, stats):
-        self.wRi, self.rot_valid, self.stats = wRi, rot_valid, stats
+    wRi: torch.Tensor
+    rot_valid: torch.Tensor
+    stats: torch.Tensor
 
 
 def rotavg_shonan(edges: torch.Tensor, aRb: torch.Tensor, kappa: Optional[torch.Tensor], edge_valid: Optional[torch.Tensor],
@@ -976,33 +995,21 @@ def rotavg_shonan(edges: torch.Tensor, aRb: torch.Tensor, kappa: Optional[torch.
     """Global rotations from relative ones by Shonan averaging with an optimality certificate (gtsfm_rotavg_shonan).
     edges (E, 2) int32 = (a, b) with aRb (E, 3, 3) float64 asking wRa aRb = wRb; kappa (E,) float64 or None (= 1).
     Runs its LM / PCG / Lanczos control flow on the host and synchronises the stream."""
-    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous() and edges.dim() == 2 and \
-        edges.shape[1] == 2
+    _check(edges, "edges", _I32, shape=(None, 2))
     n = edges.shape[0]
-    assert aRb.is_cuda and aRb.dtype == torch.float64 and aRb.is_contiguous() and aRb.numel() == 9 * n
-    if kappa is not None:
-        assert kappa.is_cuda and kappa.dtype == torch.float64 and kappa.is_contiguous() and kappa.numel() == n
-    if edge_valid is not None:
-        assert edge_valid.is_cuda and edge_valid.dtype == torch.uint8 and edge_valid.is_contiguous() and \
-            edge_valid.numel() == n
-    if wRi_init is not None:
-        assert wRi_init.is_cuda and wRi_init.dtype == torch.float64 and wRi_init.is_contiguous() and \
-            wRi_init.numel() == 9 * n_img
+    _check(aRb, "aRb", _F64, numel=9 * n)
+    _check(kappa, "kappa", _F64, numel=n, optional=True)
+    _check(edge_valid, "edge_valid", _U8, numel=n, optional=True)
+    _check(wRi_init, "wRi_init", _F64, numel=9 * n_img, optional=True)
     dev = edges.device
     wRi = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
     rot_valid = torch.empty(n_img, dtype=torch.uint8, device=dev)
     stats = torch.empty(12, dtype=torch.float64, device=dev)
     L = native.lib()
-    need = L.gtsfm_rotavg_workspace_bytes(n, int(n_img), int(p_max))
-    if workspace is None:
-        if need == 0:
-            raise native.NativeError(f"gtsfm_rotavg_shonan: unsupported shape {n} edges, {n_img} images, p_max {p_max}")
-        workspace = _workspace(need, dev)
-    ws = workspace
-    if stream is not None:
-        ws.record_stream(stream)
+    ws = _take_workspace(L.gtsfm_rotavg_workspace_bytes(n, int(n_img), int(p_max)), dev, workspace, stream,
+                         f"gtsfm_rotavg_shonan: unsupported shape {n} edges, {n_img} images, p_max {p_max}")
     rc = L.gtsfm_rotavg_shonan(_ptr(edges), _ptr(aRb), _ptr(kappa), _ptr(edge_valid), n, int(n_img), _ptr(wRi_init),
-                               int(seed) & (2 ** 64 - 1), int(p_min), int(p_max), float(optimality_threshold),
+                               _u64(seed), int(p_min), int(p_max), float(optimality_threshold),
                                float(grad_rel_tol), int(max_iterations), float(pcg_rel_tol), int(pcg_max_iter),
                                float(eig_tol), int(eig_max_steps), _ptr(ws), ws.numel(), _ptr(wRi), _ptr(rot_valid),
                                _ptr(stats), native.stream_handle(stream))

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd import device, native
+from gtsfm_amd.common import upload
 from gtsfm_amd.common.image import Image
 from gtsfm_amd.common.keypoints import Keypoints
 from gtsfm_amd.frontend.cacher.detector_descriptor_cacher import DetectorDescriptorCacher
@@ -59,9 +60,8 @@ class DeviceFeatures:
 def extract_sift_batched(detector: SIFTDetectorDescriptor, images: Sequence[Image]) -> DeviceFeatures:
     """gtsfm_sift_batched launch sequences per image size (workspace-bounded groups); features gathered into one
     padded block."""
-    native.require_gpu()
+    dev = upload.cuda_device()
     n, k = len(images), detector.max_keypoints
-    dev = torch.device("cuda")
     xy = torch.zeros((n, k, 2), dtype=torch.float32, device=dev)
     attr = torch.zeros((n, k, 3), dtype=torch.float32, device=dev)
     desc = torch.zeros((n, k, 128), dtype=torch.float32, device=dev)
@@ -105,9 +105,8 @@ def extract_superpoint_batched(detector: SuperPointDetectorDescriptor, images: S
     """gtsfm_superpoint_batched per image size in workspace-bounded groups; features gathered into one padded block
     (scores kept for SuperGlue). Image masks filter the detections on the device before the top-k, as the per-call
     plugin (reference superpoint.py:68-72)."""
-    native.require_gpu()
+    dev = upload.cuda_device()
     n, k = len(images), detector.max_keypoints
-    dev = torch.device("cuda")
     xy = torch.zeros((n, k, 2), dtype=torch.float32, device=dev)
     sc = torch.zeros((n, k), dtype=torch.float32, device=dev)
     desc = torch.zeros((n, k, 256), dtype=torch.float32, device=dev)

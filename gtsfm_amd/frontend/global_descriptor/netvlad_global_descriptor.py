@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd import device, native
+from gtsfm_amd.common import upload
 from gtsfm_amd.common.image import Image
 from gtsfm_amd.frontend.global_descriptor.global_descriptor_base import GlobalDescriptorBase
 
@@ -100,8 +101,7 @@ class NetVLADGlobalDescriptor(GlobalDescriptorBase):
     def describe_device(self, images: Sequence[Image]) -> torch.Tensor:
         """(n, 4096) f32 device tensor (n, 32768 without whitening): images grouped by size, each group in
         workspace-bounded launch sequences of gtsfm_netvlad_batched."""
-        native.require_gpu()
-        dev = torch.device("cuda")
+        dev = upload.cuda_device()
         dim = WHITE_DIM if self._whiten else DIM * CLUSTERS
         out = torch.empty((len(images), dim), dtype=torch.float32, device=dev)
         by_shape: Dict[tuple, List[int]] = {}

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd import device, native
+from gtsfm_amd.common import upload
 from gtsfm_amd.common.keypoints import Keypoints
 from gtsfm_amd.frontend.matcher.matcher_base import MatcherBase
 
@@ -49,7 +50,7 @@ def select_match_mode(d1: np.ndarray, d2: np.ndarray) -> int:
 
 def match_descriptor_pair(d1: np.ndarray, d2: np.ndarray, ratio: Optional[float]) -> np.ndarray:
     """Runs the device matcher on one pair of (already NaN-free) descriptor arrays."""
-    native.require_gpu()
+    dev = upload.cuda_device()
     d1 = np.ascontiguousarray(d1, dtype=np.float32)
     d2 = np.ascontiguousarray(d2, dtype=np.float32)
     n1, dim = d1.shape
@@ -58,7 +59,6 @@ def match_descriptor_pair(d1: np.ndarray, d2: np.ndarray, ratio: Optional[float]
     host = np.zeros((2, kmax, dim), dtype=np.float32)
     host[0, :n1] = d1
     host[1, :n2] = d2
-    dev = torch.device("cuda")
     desc = torch.from_numpy(host).to(dev)
     counts = torch.tensor([n1, n2], dtype=torch.int32, device=dev)
     pairs = torch.tensor([[0, 1]], dtype=torch.int32, device=dev)

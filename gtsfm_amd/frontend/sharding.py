@@ -148,8 +148,9 @@ def allgather_features(tensors: Sequence[torch.Tensor], n_per: int,
 class CollectiveAllGather:
     """The exchange's collective: one all_gather_into_tensor of the packed per-rank blocks over the process group
     (RCCL over xGMI under the "nccl" backend). allgather_features uses it for world > 1; passed explicitly as
-    `exchange`, it runs the collective at any world size, including 1 (tests/test_rccl_gpu.py drives the RCCL path
-    on a one-GPU box that way)."""
+    `exchange`, it runs the collective at any world size, including 1
+    (tests/test_multirank_gpu.py::test_rccl_exchange_world1_equals_plain_step drives the RCCL path on a one-GPU box
+    that way)."""
 
     def __init__(self, group: Optional[torch.distributed.ProcessGroup] = None):
         self.group = group

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from gtsfm_amd import device, native
-from gtsfm_amd.common import geometry
+from gtsfm_amd.common import geometry, upload
 from gtsfm_amd.common.keypoints import Keypoints
 from gtsfm_amd.frontend.verifier.verifier_base import VerifierBase
 
@@ -142,8 +142,7 @@ class Ransac(VerifierBase):
         Same guards and failure tuple as verify(), and the same sampler stream: every pair is keyed by pair id 0,
         as a one-pair verify() call is, so the batch reproduces verify() pair for pair.
         """
-        native.require_gpu()
-        dev = torch.device("cuda")
+        dev = upload.cuda_device()
         n = len(keypoints_list)
         kmax = max([len(k) for k in keypoints_list] + [1])
         kp = np.zeros((n, kmax, 2), np.float32)

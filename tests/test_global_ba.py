@@ -190,7 +190,7 @@ def restated_kernel(monkeypatch):
     import torch
 
     from gtsfm_amd import device, native
-    from gtsfm_amd.bundle import bundle_adjustment as ba
+    from gtsfm_amd.common import upload
 
     calls = []
 
@@ -205,7 +205,7 @@ def restated_kernel(monkeypatch):
 
     monkeypatch.setattr(device, "global_ba", fake)
     monkeypatch.setattr(native, "require_gpu", lambda: None)
-    monkeypatch.setattr(ba, "_ba_device", lambda: torch.device("cpu"))
+    monkeypatch.setattr(upload, "cuda_device", lambda like=None: torch.device("cpu"))
     return calls
 
 
