@@ -23,6 +23,7 @@ from gtsfm_amd.frontend.triangulation_options import (  # noqa: F401  (re-export
 )
 
 ArrayLike = Union[np.ndarray, torch.Tensor]
+DeviceCameras = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]
 
 MODE_TO_NATIVE = {
     TriangulationSamplingMode.NO_RANSAC: native.GTSFM_TRI_NO_RANSAC,
@@ -72,16 +73,26 @@ def camera_arrays(track_camera_dict: Dict[int, object], num_images: Optional[int
 class Point3dInitializer:
     """Initialises landmark points by triangulation, with or without RANSAC over the track's measurement pairs."""
 
-    def __init__(self, track_camera_dict: Dict[int, object], options: TriangulationOptions, seed: int = 0) -> None:
-        if len(track_camera_dict) == 0:
-            raise ValueError("No camera positions were estimated, so triangulation is not feasible.")
+    def __init__(self, track_camera_dict: Union[Dict[int, object], DeviceCameras], options: TriangulationOptions,
+                 seed: int = 0) -> None:
+        """track_camera_dict: {image index: camera or None}, or the tuple (wRc (n_img, 3, 3), wtc (n_img, 3),
+        intrinsics (n_img, 3) float64, cam_valid (n_img,) uint8) of device tensors that
+        BundleAdjustmentOptimizer.run_ba_arrays takes too; the tuple is used as it is, with no host copy."""
         self.track_camera_dict = track_camera_dict
         self.options = options
         self.seed = int(seed)
+        if not isinstance(track_camera_dict, dict):
+            self._cams = None
+            self._cams_dev = tuple(track_camera_dict)
+            return
+        if len(track_camera_dict) == 0:
+            raise ValueError("No camera positions were estimated, so triangulation is not feasible.")
         self._cams = camera_arrays(track_camera_dict)
         self._cams_dev = None
 
     def _device_cameras(self, dev: torch.device):
+        if self._cams is None:
+            return self._cams_dev
         if self._cams_dev is None or self._cams_dev[0].device != dev:
             c = self._cams
             self._cams_dev = tuple(upload.to_device(a, dev) for a in (c.wRc, c.wtc, c.intrinsics, c.valid))

@@ -849,6 +849,62 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
 
 
 @dataclass(eq=False)
+class BaInputResult:
+    """Outputs of assemble_ba_input, all on the device: cam_keep (n_img,) and track_keep (T,) uint8, track_len (T,)
+    int32, stats (6,) int64 in the order of native.BA_INPUT_STATS_FIELDS."""
+
+    cam_keep: torch.Tensor
+    track_keep: torch.Tensor
+    track_len: torch.Tensor
+    stats: torch.Tensor
+
+
+def assemble_ba_input(track_offsets: torch.Tensor, track_img: torch.Tensor, track_valid: Optional[torch.Tensor],
+                      meas_inlier: Optional[torch.Tensor], cam_valid: Optional[torch.Tensor], n_img: int,
+                      extra_edges: Optional[torch.Tensor] = None, n_tracks: Optional[int] = None,
+                      n_tracks_dev: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                      workspace: Optional[torch.Tensor] = None,
+                      workspace_bytes: Optional[int] = None) -> BaInputResult:
+    """The cameras and tracks that go into bundle adjustment: the largest connected component of cameras joined by
+    the accepted tracks, and the tracks wholly inside it (gtsfm_assemble_ba_input; semantics in include/gtsfm_hip.h).
+
+    track_offsets (>= T + 1,) and track_img (n_meas,) int32 as for triangulate_tracks; track_valid (T,) uint8 or bool
+    or None, meas_inlier (n_meas,) uint8 or None (the triangulation's inlier bytes), cam_valid (n_img,) uint8 or None,
+    extra_edges (n_extra, 2) int32 or None. Nothing is copied to the host or synchronised. workspace_bytes below the
+    query's value is passed as is (tests of the capacity error)."""
+    _check(n_tracks_dev, "n_tracks_dev", _I64, min_numel=1, optional=True)
+    _check(track_offsets, "track_offsets", _I32)
+    _check(track_img, "track_img", _I32)
+    n_meas = track_img.numel()
+    T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
+    assert 0 <= T <= max(track_offsets.numel() - 1, 0), f"n_tracks {T} for {track_offsets.numel()} track_offsets"
+    n_img = int(n_img)
+    if track_valid is not None and track_valid.dtype == torch.bool:
+        track_valid = track_valid.to(torch.uint8)
+    _check(track_valid, "track_valid", _U8, min_numel=T, optional=True)
+    _check(meas_inlier, "meas_inlier", _U8, numel=n_meas, optional=True)
+    _check(cam_valid, "cam_valid", _U8, numel=n_img, optional=True)
+    _check(extra_edges, "extra_edges", _I32, shape=(None, 2), optional=True)
+    n_extra = 0 if extra_edges is None else extra_edges.shape[0]
+    dev = track_offsets.device
+    cam_keep = torch.empty(n_img, dtype=torch.uint8, device=dev)
+    track_keep = torch.empty(T, dtype=torch.uint8, device=dev)
+    track_len = torch.empty(T, dtype=torch.int32, device=dev)
+    stats = torch.empty(6, dtype=torch.int64, device=dev)
+    L = native.lib()
+    ws = _take_workspace(L.gtsfm_assemble_ba_input_workspace_bytes(T, n_img), dev, workspace, stream,
+                         None if T == 0 or n_img == 0 else
+                         f"gtsfm_assemble_ba_input: unsupported shape {T} tracks, {n_img} images")
+    rc = L.gtsfm_assemble_ba_input(_ptr(track_offsets), _ptr(track_img), T, _ptr(n_tracks_dev), n_meas,
+                                   _ptr(track_valid), _ptr(meas_inlier), _ptr(cam_valid), n_img,
+                                   _ptr(extra_edges) if n_extra else None, n_extra, _ptr(ws),
+                                   ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(cam_keep),
+                                   _ptr(track_keep), _ptr(track_len), _ptr(stats), native.stream_handle(stream))
+    native.check(rc, "gtsfm_assemble_ba_input")
+    return BaInputResult(cam_keep, track_keep, track_len, stats)
+
+
+@dataclass(eq=False)
 class TransAvgMeasurements:
     """Outputs of transavg_measurements, all on the device: key (n_edges + n_meas, 2) int32, dir (.., 3) float64, valid
     (..,) uint8, selected (n_tracks,) int32, cam_valid (n_img,) uint8, counts (4,) int64 = valid camera edges, track

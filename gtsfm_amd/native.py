@@ -72,6 +72,8 @@ RA_STATUS_UNCERTIFIED = 2  # p_max reached without a certificate; the rotations 
 RA_STATUS_NOT_FINITE = 3
 RA_STATS_FIELDS = ("initial_cost", "final_cost", "final_p", "min_eigenvalue", "eigen_residual", "lm_iterations",
                    "pcg_iterations", "pcg_cap_hits", "lanczos_steps", "cameras_valid", "edges_used", "status")
+BA_INPUT_STATS_FIELDS = ("components", "cameras_kept", "tracks_kept", "measurements_kept", "accepted_tracks",
+                         "valid_cameras")
 TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
                     "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
@@ -199,6 +201,12 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_uint64, c_int, c_int, c_double, c_double,
          c_int, c_double, c_int, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_assemble_ba_input_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "gtsfm_assemble_ba_input": (
+        c_int,
+        [c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
 }
 

@@ -34,6 +34,9 @@
  *                              gtsfm/utils/reprojection.py:48-83 and gtsfm/utils/tracks.py:82-102
  *   gtsfm_global_ba*        <- gtsfm/bundle/bundle_adjustment.py:58-397 BundleAdjustmentOptimizer.run_ba,
  *                              gtsfm/bundle/global_ba.py and gtsfm/common/gtsfm_data.py:389-427 filter_landmarks
+ *   gtsfm_assemble_ba_input* <- gtsfm/data_association/data_assoc.py:123-160 assemble_gtsfm_data_from_tracks (no
+ *                              metrics), gtsfm/common/gtsfm_data.py:238-317 select_largest_connected_component and
+ *                              from_selected_cameras, gtsfm/utils/graph.py:20-39
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -55,8 +58,8 @@ extern "C" {
  * ---------------------------------------------------------------------------------------------- */
 /* ABI version (major*100 + minor); a binding built against this header checks that the library
  * returns GTSFM_HIP_ABI_VERSION before binding anything else. */
-/* Stays 407 with gtsfm_rotavg_* added: new symbols only, no existing signature or meaning changed, so no caller of
- * a 407 library breaks. */
+/* Stays 407 with gtsfm_rotavg_* and gtsfm_assemble_ba_input* added: new symbols only, no existing signature or
+ * meaning changed, so no caller of a 407 library breaks. */
 #define GTSFM_HIP_ABI_VERSION 407
 int gtsfm_hip_abi_version(void);
 /* Name of the offload target the kernels were compiled for (e.g. "gfx950"). */
@@ -753,6 +756,61 @@ int gtsfm_rotavg_shonan(const int* d_edges, const double* d_aRb, const double* d
                         double optimality_threshold, double grad_rel_tol, int max_iterations, double pcg_rel_tol,
                         int pcg_max_iter, double eig_tol, int eig_max_steps, void* d_workspace, size_t workspace_bytes,
                         double* d_wRi, uint8_t* d_rot_valid, double* d_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * The input of global bundle adjustment: gtsfm/data_association/data_assoc.py:123-160
+ * assemble_gtsfm_data_from_tracks without its metrics (the valid tracks, then
+ * GtsfmData.select_largest_connected_component, gtsfm/common/gtsfm_data.py:238-274, get_nodes_in_largest_connected_
+ * component, gtsfm/utils/graph.py:20-39, and from_selected_cameras, gtsfm_data.py:286-317). It sits between
+ * gtsfm_triangulate_tracks and gtsfm_global_ba: the masks it writes are the d_cam_valid and d_track_valid of the latter.
+ *
+ * Inputs, as the upstream calls leave them: the track CSR d_track_offsets[n_tracks + 1] (ascending over the tracks in
+ * use, as gtsfm_tracks_from_matches writes it) and d_track_img[n_meas]; n_tracks is the track count or, with d_n_tracks
+ * non-NULL, a capacity (min(n_tracks, d_n_tracks[0]) is used, read on the device); d_track_valid[n_tracks], the `valid`
+ * byte of DataAssociation.run_triangulation_arrays, or NULL (all); d_meas_inlier[n_meas], the triangulation's inlier
+ * bytes, or NULL (all); d_cam_valid[n_img] or NULL (all); d_extra_edges[n_extra][2] int32 or NULL with n_extra == 0: the
+ * reference's extra_camera_edges, the keys of the relative-pose priors. An extra edge with an end outside [0, n_img)
+ * or at an invalid camera is ignored.
+ * Semantics.
+ *   Accepted track: its valid byte is set and its offsets lie inside [0, n_meas]. Its measurements are those whose
+ *     inlier byte is set (the reference's SfmTrack holds inliers only). valid already requires exit code 0, so the
+ *     reference's skip of CHEIRALITY_FAILURE tracks (data_assoc.py:134-135) needs no test of its own.
+ *   Graph nodes: the cameras named by an accepted track of at least two measurements, and the ends of the extra edges
+ *     in use. itertools.combinations of one camera adds nothing (gtsfm_data.py:259), so a camera seen only in
+ *     one-measurement tracks is in no component. A camera with d_cam_valid 0 that a track names is a node and counts
+ *     in its component's size, as in the reference, whose graph is built from the tracks alone; it is never kept. A
+ *     measurement whose image index is outside [0, n_img) is in no camera: it joins nothing and its track is not kept.
+ *   Graph edges: all cameras of one accepted track are joined; the two ends of each extra edge are joined.
+ *   Selected component: the one with the most nodes; among equals, the one whose first contributing item has the
+ *     smallest index, where track t has index t and extra edge e has index n_tracks + e. That is what
+ *     max(nx.connected_components(G), key=len) returns for a graph built by add_edges_from over the tracks in ascending
+ *     order and then the extra edges: networkx keeps nodes in insertion order and yields the components in the order of
+ *     their first node, and max keeps the first maximum. Verified against networkx 3.4.2 (tests/test_multi_view.py).
+ *     gtsfm_rotavg_shonan's rule for equal components (the lowest camera index) is another one, on purpose: there the
+ *     reference's graph is built from a dict of pairs.
+ *   No edge at all: the result is empty (gtsfm_data.py:265-266), whatever the tracks.
+ * Outputs (caller-owned): d_cam_keep[n_img] bytes: the camera is valid and lies in the selected component;
+ * d_track_keep[n_tracks] bytes: the track is accepted and every one of its inlier measurements is in a kept camera
+ * (from_selected_cameras, :299-315; an accepted one-measurement track in a kept camera is kept); d_track_len[n_tracks]
+ * int32: the inlier count of a kept track, else 0 (the reference's 3d_tracks_length); d_stats[6] int64 = { components,
+ * cameras kept, tracks kept, measurements kept, accepted tracks, valid cameras }. Entries of tracks past the count in
+ * use are 0.
+ * Integers only: a lock-free union-find over the cameras with one lane per measurement, per-root sizes and first items
+ * by integer atomicAdd / atomicMin, one workgroup that reduces the roots to the winner. The outputs depend on the
+ * input set alone and are byte-identical from launch to launch. Nothing allocates or synchronises.
+ * Workspace: 17 bytes per camera and 8 per track. n_tracks, n_meas or n_img == 0 returns GTSFM_OK with zeroed outputs
+ * and launches no kernel. A negative size, n_tracks + n_extra or n_meas + n_extra >= 2^31 - 1 or a NULL required
+ * pointer returns GTSFM_ERR_ARG; a workspace smaller than the query's answer returns GTSFM_ERR_CAPACITY.
+ * ---------------------------------------------------------------------------------------------- */
+/* 0 for an empty shape (a size <= 0) or an unsupported one (n_tracks >= 2^31 - 1). */
+size_t gtsfm_assemble_ba_input_workspace_bytes(long long n_tracks, int n_img);
+
+int gtsfm_assemble_ba_input(const int* d_track_offsets, const int* d_track_img, long long n_tracks,
+                            const long long* d_n_tracks, long long n_meas, const uint8_t* d_track_valid,
+                            const uint8_t* d_meas_inlier, const uint8_t* d_cam_valid, int n_img,
+                            const int* d_extra_edges, int n_extra, void* d_workspace, size_t workspace_bytes,
+                            uint8_t* d_cam_keep, uint8_t* d_track_keep, int* d_track_len, long long* d_stats,
+                            void* stream);
 
 #ifdef __cplusplus
 }
