@@ -1071,3 +1071,192 @@ def rotavg_shonan(edges: torch.Tensor, aRb: torch.Tensor, kappa: Optional[torch.
                                _ptr(stats), native.stream_handle(stream))
     native.check(rc, "gtsfm_rotavg_shonan")
     return RotAvgResult(wRi, rot_valid, stats)
+
+
+@dataclass(eq=False)
+class MvsViewsResult:
+    """Outputs of mvs_select_views, all on the device and sized by n_img (the caller slices by stats[0] = n_valid):
+    img_to_pm and pm_to_img (n_img,) int32, scores (n_img, n_img) int64 in units of 2^-40, src_views (n_img,
+    max_num_views - 1) int32, depth_range (n_img, 2) float64, stats (4,) int64 in the order of
+    native.MVS_VIEWS_STATS_FIELDS."""
+
+    img_to_pm: torch.Tensor
+    pm_to_img: torch.Tensor
+    scores: torch.Tensor
+    src_views: torch.Tensor
+    depth_range: torch.Tensor
+    stats: torch.Tensor
+
+
+def mvs_select_views(track_offsets: torch.Tensor, track_img: torch.Tensor, point: torch.Tensor,
+                     track_keep: Optional[torch.Tensor], meas_inlier: Optional[torch.Tensor], wRc: torch.Tensor,
+                     wtc: torch.Tensor, cam_keep: Optional[torch.Tensor], max_num_views: int = 5,
+                     n_tracks: Optional[int] = None, stream: Optional[torch.cuda.Stream] = None,
+                     workspace: Optional[torch.Tensor] = None,
+                     workspace_bytes: Optional[int] = None) -> MvsViewsResult:
+    """Source views and depth ranges of every valid camera from the tracks (gtsfm_mvs_select_views; semantics in
+    include/gtsfm_hip.h). Nothing is copied to the host or synchronised. workspace_bytes below the query's value is
+    passed as is (tests of the capacity error)."""
+    _check(track_offsets, "track_offsets", _I32)
+    _check(track_img, "track_img", _I32)
+    n_meas = track_img.numel()
+    T = max(track_offsets.numel() - 1, 0) if n_tracks is None else int(n_tracks)
+    assert 0 <= T <= max(track_offsets.numel() - 1, 0), f"n_tracks {T} for {track_offsets.numel()} track_offsets"
+    n_img = wtc.numel() // 3
+    _check(wRc, "wRc", _F64, numel=9 * n_img)
+    _check(wtc, "wtc", _F64, numel=3 * n_img)
+    _check(point, "point", _F64, min_numel=3 * T)
+    if track_keep is not None and track_keep.dtype == torch.bool:
+        track_keep = track_keep.to(torch.uint8)
+    _check(track_keep, "track_keep", _U8, min_numel=T, optional=True)
+    _check(meas_inlier, "meas_inlier", _U8, numel=n_meas, optional=True)
+    _check(cam_keep, "cam_keep", _U8, numel=n_img, optional=True)
+    S = int(max_num_views) - 1
+    dev = wtc.device
+    r = MvsViewsResult(torch.empty(n_img, dtype=_I32, device=dev), torch.empty(n_img, dtype=_I32, device=dev),
+                       torch.empty((n_img, n_img), dtype=_I64, device=dev),
+                       torch.empty((n_img, max(S, 0)), dtype=_I32, device=dev),
+                       torch.empty((n_img, 2), dtype=_F64, device=dev), torch.empty(4, dtype=_I64, device=dev))
+    L = native.lib()
+    ws = _take_workspace(L.gtsfm_mvs_select_views_workspace_bytes(T, n_meas, n_img), dev, workspace, stream,
+                         None if T == 0 or n_meas == 0 or n_img == 0 else
+                         f"gtsfm_mvs_select_views: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
+    rc = L.gtsfm_mvs_select_views(_ptr(track_offsets), _ptr(track_img), T, n_meas, _ptr(point), _ptr(track_keep),
+                                  _ptr(meas_inlier), _ptr(wRc), _ptr(wtc), _ptr(cam_keep), n_img, int(max_num_views),
+                                  _ptr(ws), ws.numel() if workspace_bytes is None else int(workspace_bytes),
+                                  _ptr(r.img_to_pm), _ptr(r.pm_to_img), _ptr(r.scores),
+                                  _ptr(r.src_views) if S > 0 else None, _ptr(r.depth_range), _ptr(r.stats),
+                                  native.stream_handle(stream))
+    native.check(rc, "gtsfm_mvs_select_views")
+    return r
+
+
+@dataclass(eq=False)
+class MvsFusedResult:
+    """Outputs of mvs_fuse_depth, all on the device: fused (n, H, W) float32, mask (n, H, W) uint8 (bit 0 geometric,
+    bit 1 confidence, bit 2 joint), counts (n, 4) int64 in the order of native.MVS_FUSE_COUNT_FIELDS, err (n, 3)
+    float64 = (sum, min, max) of the counted reprojection errors."""
+
+    fused: torch.Tensor
+    mask: torch.Tensor
+    counts: torch.Tensor
+    err: torch.Tensor
+
+
+def mvs_fuse_depth(depth: torch.Tensor, confidence: torch.Tensor, wRc: torch.Tensor, wtc: torch.Tensor,
+                   intrinsics: torch.Tensor, src_views: torch.Tensor, pixel_thresh: float = 1.0,
+                   depth_thresh: float = 0.01, min_confidence: float = 0.8, min_consistent_views: int = 1,
+                   stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                   workspace_bytes: Optional[int] = None) -> MvsFusedResult:
+    """Geometric-consistency filter and fusion of the depth maps of all views (gtsfm_mvs_fuse_depth). depth and
+    confidence (n, H, W) float32, cameras per view, src_views (n, S) int32. Nothing is copied to the host or
+    synchronised."""
+    _check(depth, "depth", _F32, shape=(None, None, None))
+    n, H, W = depth.shape
+    _check(confidence, "confidence", _F32, shape=(n, H, W))
+    assert _check_cameras(wRc, wtc, intrinsics, None) == n, f"{intrinsics.numel() // 3} cameras for {n} views"
+    _check(src_views, "src_views", _I32, shape=(n, None))
+    S = src_views.shape[1]
+    dev = depth.device
+    r = MvsFusedResult(torch.empty((n, H, W), dtype=_F32, device=dev), torch.empty((n, H, W), dtype=_U8, device=dev),
+                       torch.empty((n, 4), dtype=_I64, device=dev), torch.empty((n, 3), dtype=_F64, device=dev))
+    L = native.lib()
+    ws = _take_workspace(L.gtsfm_mvs_fuse_depth_workspace_bytes(n, H, W), dev, workspace, stream,
+                         None if n == 0 or H == 0 or W == 0 else
+                         f"gtsfm_mvs_fuse_depth: unsupported shape {n} views of {H} x {W}")
+    rc = L.gtsfm_mvs_fuse_depth(_ptr(depth), _ptr(confidence), n, H, W, _ptr(wRc), _ptr(wtc), _ptr(intrinsics),
+                                _ptr(src_views) if S else None, S, float(pixel_thresh), float(depth_thresh),
+                                float(min_confidence), int(min_consistent_views), _ptr(ws),
+                                ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(r.fused),
+                                _ptr(r.mask), _ptr(r.counts), _ptr(r.err), native.stream_handle(stream))
+    native.check(rc, "gtsfm_mvs_fuse_depth")
+    return r
+
+
+def mvs_gather_points(fused: torch.Tensor, mask: torch.Tensor, wRc: torch.Tensor, wtc: torch.Tensor,
+                      intrinsics: torch.Tensor, images: torch.Tensor, view_image: Optional[torch.Tensor],
+                      capacity: int, stream: Optional[torch.cuda.Stream] = None,
+                      workspace: Optional[torch.Tensor] = None, workspace_bytes: Optional[int] = None,
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The coloured points of the joint pixels in canonical order (gtsfm_mvs_gather_points): views ascending, then
+    row-major. images (n_images, h, w, 3) uint8 with h >= H and w >= W, view_image (n,) int32 or None. Returns points
+    (capacity, 3) float64, colors (capacity, 3) uint8 and view_offset (n + 1,) int64; capacity is the caller's, read
+    from mvs_fuse_depth's counts. Nothing is copied to the host or synchronised."""
+    _check(fused, "fused", _F32, shape=(None, None, None))
+    n, H, W = fused.shape
+    _check(mask, "mask", _U8, shape=(n, H, W))
+    assert _check_cameras(wRc, wtc, intrinsics, None) == n, f"{intrinsics.numel() // 3} cameras for {n} views"
+    _check(images, "images", _U8, shape=(None, None, None, 3))
+    _check(view_image, "view_image", _I32, numel=n, optional=True)
+    capacity = int(capacity)
+    dev = fused.device
+    points = torch.empty((max(capacity, 0), 3), dtype=_F64, device=dev)
+    colors = torch.empty((max(capacity, 0), 3), dtype=_U8, device=dev)
+    view_offset = torch.empty(n + 1, dtype=_I64, device=dev)
+    L = native.lib()
+    ws = _take_workspace(L.gtsfm_mvs_gather_points_workspace_bytes(n, H, W), dev, workspace, stream,
+                         None if n == 0 or H == 0 or W == 0 else
+                         f"gtsfm_mvs_gather_points: unsupported shape {n} views of {H} x {W}")
+    rc = L.gtsfm_mvs_gather_points(_ptr(fused), _ptr(mask), n, H, W, _ptr(wRc), _ptr(wtc), _ptr(intrinsics),
+                                   _ptr(images), _ptr(view_image), images.shape[0], images.shape[1], images.shape[2],
+                                   capacity, _ptr(ws), ws.numel() if workspace_bytes is None else int(workspace_bytes),
+                                   _ptr(points) if capacity > 0 else None, _ptr(colors) if capacity > 0 else None,
+                                   _ptr(view_offset), native.stream_handle(stream))
+    native.check(rc, "gtsfm_mvs_gather_points")
+    return points, colors, view_offset
+
+
+def mvs_voxel_stats(points: torch.Tensor, stream: Optional[torch.cuda.Stream] = None,
+                    workspace: Optional[torch.Tensor] = None, workspace_bytes: Optional[int] = None) -> torch.Tensor:
+    """(18,) float64 on the device: mean, scatter / (N - 1), min and max bound of points (N, 3) float64
+    (gtsfm_mvs_voxel_stats)."""
+    _check(points, "points", _F64, shape=(None, 3))
+    n = points.shape[0]
+    stats = torch.empty(18, dtype=_F64, device=points.device)
+    L = native.lib()
+    ws = _take_workspace(L.gtsfm_mvs_voxel_stats_workspace_bytes(n), points.device, workspace, stream)
+    rc = L.gtsfm_mvs_voxel_stats(_ptr(points), n, _ptr(ws), ws.numel() if workspace_bytes is None else
+                                 int(workspace_bytes), _ptr(stats), native.stream_handle(stream))
+    native.check(rc, "gtsfm_mvs_voxel_stats")
+    return stats
+
+
+@dataclass(eq=False)
+class MvsVoxelResult:
+    """Outputs of mvs_voxel_downsample, all on the device with N rows of which the first n_voxels[0] are used: points
+    (N, 3) float64, colors (N, 3) uint8, keys (N,) int64 ascending, count (N,) int32, n_voxels (1,) int64."""
+
+    points: torch.Tensor
+    colors: torch.Tensor
+    keys: torch.Tensor
+    count: torch.Tensor
+    n_voxels: torch.Tensor
+
+
+def mvs_voxel_downsample(points: torch.Tensor, colors: torch.Tensor, stats: torch.Tensor, voxel_size: float,
+                         stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                         workspace_bytes: Optional[int] = None) -> MvsVoxelResult:
+    """One point per occupied voxel, in ascending key order: gtsfm_mvs_voxel_keys, a stable torch.sort of the keys
+    (plumbing) and gtsfm_mvs_voxel_downsample's segmented mean. stats is mvs_voxel_stats' result (its min bound is the
+    grid's origin); voxel_size > 0. Nothing is copied to the host or synchronised."""
+    _check(points, "points", _F64, shape=(None, 3))
+    n = points.shape[0]
+    _check(colors, "colors", _U8, shape=(n, 3))
+    _check(stats, "stats", _F64, numel=18)
+    dev = points.device
+    L = native.lib()
+    keys = torch.empty(n, dtype=_I64, device=dev)
+    native.check(L.gtsfm_mvs_voxel_keys(_ptr(points), n, _ptr(stats), float(voxel_size), _ptr(keys),
+                                        native.stream_handle(stream)), "gtsfm_mvs_voxel_keys")
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        sorted_keys, perm = torch.sort(keys, stable=True)  # on the stream of the two calls around it
+    r = MvsVoxelResult(torch.empty((n, 3), dtype=_F64, device=dev), torch.empty((n, 3), dtype=_U8, device=dev),
+                       torch.empty(n, dtype=_I64, device=dev), torch.empty(n, dtype=_I32, device=dev),
+                       torch.empty(1, dtype=_I64, device=dev))
+    ws = _take_workspace(L.gtsfm_mvs_voxel_downsample_workspace_bytes(n), dev, workspace, stream)
+    rc = L.gtsfm_mvs_voxel_downsample(_ptr(points), _ptr(colors), _ptr(sorted_keys), _ptr(perm), n, _ptr(ws),
+                                      ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(r.points),
+                                      _ptr(r.colors), _ptr(r.keys), _ptr(r.count), _ptr(r.n_voxels),
+                                      native.stream_handle(stream))
+    native.check(rc, "gtsfm_mvs_voxel_downsample")
+    return r

@@ -74,6 +74,9 @@ RA_STATS_FIELDS = ("initial_cost", "final_cost", "final_p", "min_eigenvalue", "e
                    "pcg_iterations", "pcg_cap_hits", "lanczos_steps", "cameras_valid", "edges_used", "status")
 BA_INPUT_STATS_FIELDS = ("components", "cameras_kept", "tracks_kept", "measurements_kept", "accepted_tracks",
                          "valid_cameras")
+MVS_VIEWS_STATS_FIELDS = ("valid_cameras", "source_views", "cameras_without_depth", "score_terms")
+MVS_FUSE_COUNT_FIELDS = ("geometric_pixels", "confidence_pixels", "joint_pixels", "reprojection_errors")
+MVS_SCORE_SCALE = 2.0 ** 40  # gtsfm_mvs_select_views' scores are integers in units of 2^-40
 TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
                     "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
@@ -207,6 +210,33 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
          c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_mvs_select_views_workspace_bytes": (c_size_t, [c_longlong, c_longlong, c_int]),
+    "gtsfm_mvs_select_views": (
+        c_int,
+        [c_void_p, c_void_p, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_mvs_fuse_depth_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gtsfm_mvs_fuse_depth": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double,
+         c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_mvs_gather_points_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gtsfm_mvs_gather_points": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+         c_longlong, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_mvs_voxel_stats_workspace_bytes": (c_size_t, [c_longlong]),
+    "gtsfm_mvs_voxel_stats": (c_int, [c_void_p, c_longlong, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "gtsfm_mvs_voxel_keys": (c_int, [c_void_p, c_longlong, c_void_p, c_double, c_void_p, c_void_p]),
+    "gtsfm_mvs_voxel_downsample_workspace_bytes": (c_size_t, [c_longlong]),
+    "gtsfm_mvs_voxel_downsample": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p],
     ),
 }
 

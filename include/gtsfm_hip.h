@@ -37,6 +37,10 @@
  *   gtsfm_assemble_ba_input* <- gtsfm/data_association/data_assoc.py:123-160 assemble_gtsfm_data_from_tracks (no
  *                              metrics), gtsfm/common/gtsfm_data.py:238-317 select_largest_connected_component and
  *                              from_selected_cameras, gtsfm/utils/graph.py:20-39
+ *   gtsfm_mvs_*             <- gtsfm/densify/patchmatchnet_data.py:78-162 select_src_views_depth_ranges,
+ *                              gtsfm/densify/mvs_patchmatchnet.py:201-437 filter_depth with
+ *                              thirdparty/patchmatchnet/eval.py:11-125, gtsfm/densify/mvs_base.py:75-92 and
+ *                              gtsfm/densify/mvs_utils.py:148-221 (everything around the depth network)
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -811,6 +815,160 @@ int gtsfm_assemble_ba_input(const int* d_track_offsets, const int* d_track_img, 
                             const int* d_extra_edges, int n_extra, void* d_workspace, size_t workspace_bytes,
                             uint8_t* d_cam_keep, uint8_t* d_track_keep, int* d_track_len, long long* d_stats,
                             void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Dense multi-view stereo around a depth estimator (gtsfm/densify/). The depth network is not part of this library:
+ * these calls choose its inputs and turn its depth and confidence maps into a point cloud. GTSFM_HIP_ABI_VERSION stays
+ * 407 with gtsfm_mvs_* added: new symbols only.
+ *
+ * Conventions shared by the five blocks below. A camera is wRc[9] (row-major, camera to world), wtc[3] (its centre)
+ * and intrinsics (f, u0, v0), all float64: X_cam = wRc' (X - wtc), u = f x / z + u0, v = f y / z + v0. Pixel (x, y)
+ * is column x of row y, at integer coordinates, as in the reference's meshgrid. "View" means pm_i, the dense index of
+ * a valid camera (below); per-view arrays are indexed by pm_i.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Source views and depth ranges: gtsfm/densify/patchmatchnet_data.py:78-162 select_src_views_depth_ranges (a triple
+ * Python loop over tracks and measurement pairs with GTSAM calls) and :55-63 (the pm_i maps), with
+ * gtsfm/densify/mvs_utils.py:21-50 and :96-123.
+ *
+ * Inputs: the track CSR d_track_offsets[n_tracks + 1] (ascending) and d_track_img[n_meas]; d_point[n_tracks][3];
+ * d_track_keep[n_tracks] and d_meas_inlier[n_meas] bytes, NULL = all; d_wRc, d_wtc per image; d_cam_keep[n_img] bytes,
+ * NULL = all; max_num_views >= 1 (the reference's num_views, 5).
+ * Valid cameras are the kept ones, numbered densely in ascending image index: pm_i. d_img_to_pm[n_img] holds pm_i or
+ * -1, d_pm_to_img[n_img] the image of pm_i = 0 .. n_valid - 1 and -1 after them. A measurement counts when its track
+ * is kept and lies inside [0, n_meas], its inlier byte is set and its image is a valid camera.
+ * Pair score: for every kept track, every unordered pair of its counting measurements in two different valid cameras
+ *   a, b adds piecewise_gaussian(theta) to score[a][b] and score[b][a]. theta, in degrees and fp64, is the angle at the
+ *   3D point between the rays to the two camera centres: both rays normalised, the dot product clipped to [-1, 1],
+ *   acos, times 180 / pi. The Gaussian is exp(-(theta - 5)^2 / (2 sigma^2)) with sigma 1 for theta <= 5 and 10 above.
+ *   Each term is added as llround(score 2^40) with a 64-bit integer atomic, so the matrix is the same bytes from launch
+ *   to launch: d_scores[n_img][n_img] int64 with row stride n_img, pm-indexed, of which the leading n_valid x n_valid
+ *   block is used; divide by 2^40. The diagonal is 0 and never chosen (the reference holds -inf there). A term that is
+ *   not a number (the point at a camera centre) is skipped. Two measurements of one track in the same camera add
+ *   nothing (the reference would add to the diagonal).
+ * Source views: V = min(max_num_views, n_valid); row r of d_src_views[n_img][max_num_views - 1] holds the V - 1
+ *   other views of highest score, descending, and -1 after them; rows from n_valid on are -1. Equal scores go to the
+ *   lower pm_i. This rule is ours: the reference's np.argsort(-scores) is not stable, so among ties, and zero scores
+ *   tie often, its order is unspecified. A zero-score view is still chosen when nothing better exists, as in the
+ *   reference.
+ * Depth range: the depths of camera r are the third component of wRc' (X - wtc), fp64, over its counting
+ *   measurements. d_depth_range[n_img][2] = (P1, P99) of them with np.percentile's default linear interpolation: virtual
+ *   index (n - 1) q, g its fraction, a + (b - a) g for g < 0.5 and b - (b - a) (1 - g) otherwise. Any count works: the
+ *   order statistics come from a radix select over the list in global memory, not from a sort. A valid camera with no
+ *   counting measurement gets (NaN, NaN) and counts in d_stats[2]; the reference would raise there. Rows from n_valid
+ *   on are 0.
+ * d_stats[4] int64 = { n_valid, V - 1, valid cameras without a depth, score terms added (one per pair) }.
+ * The caller reads n_valid from d_stats to slice the outputs; the call itself neither allocates nor synchronises.
+ * Workspace: 12 bytes per image and 8 per measurement. n_tracks, n_meas or n_img == 0 returns GTSFM_OK with every
+ * output zeroed (n_valid 0) and launches no kernel. A negative size, n_tracks or n_meas >= 2^31 - 1, n_img > 46340
+ * (n_img^2 must fit an int), max_num_views < 1 or > 65536 or a NULL required pointer: GTSFM_ERR_ARG; a short workspace:
+ * GTSFM_ERR_CAPACITY. */
+/* 0 for an empty or unsupported shape. */
+size_t gtsfm_mvs_select_views_workspace_bytes(long long n_tracks, long long n_meas, int n_img);
+
+int gtsfm_mvs_select_views(const int* d_track_offsets, const int* d_track_img, long long n_tracks, long long n_meas,
+                           const double* d_point, const uint8_t* d_track_keep, const uint8_t* d_meas_inlier,
+                           const double* d_wRc, const double* d_wtc, const uint8_t* d_cam_keep, int n_img,
+                           int max_num_views, void* d_workspace, size_t workspace_bytes, int* d_img_to_pm,
+                           int* d_pm_to_img, long long* d_scores, int* d_src_views, double* d_depth_range,
+                           long long* d_stats, void* stream);
+
+/* Depth filtering and fusion: gtsfm/densify/mvs_patchmatchnet.py:201-371 filter_depth and :374-437
+ * compute_filtered_reprojection_error over thirdparty/patchmatchnet/eval.py:11-76 reproject_with_depth and :79-125
+ * check_geometric_consistency (per (reference, source) pair two full-frame cv2.remap reprojections on the host).
+ *
+ * Inputs: d_depth and d_confidence [n_views][height][width] float32; cameras per view; d_src_views[n_views][n_src]
+ * int32 (an entry outside [0, n_views) is no source); the reference's thresholds are pixel_thresh 1.0, depth_thresh
+ * 0.01, min_confidence 0.8, min_consistent_views 1.
+ * Per (pixel (x, y) of view r with depth d_ref, source s), geometry in fp64:
+ *   X_r = ((x - u0_r) / f_r d_ref, (y - v0_r) / f_r d_ref, d_ref); X_s = wRc_s' ((wRc_r X_r + wtc_r) - wtc_s);
+ *   (u_s, v_s) its projection. The source depth is sampled bilinearly at (float32(u_s), float32(v_s)) in float32,
+ *   ((v00 (1 - ax)) (1 - ay) + (v10 ax) (1 - ay)) + ((v01 (1 - ax)) ay + (v11 ax) ay), with a constant-0 border: a tap
+ *   outside the map is 0, so samples within one pixel of the border blend with 0 and samples further out (or not finite)
+ *   are 0. The sample is back-projected with the unrounded (u_s, v_s), brought to the frame of r the same way and
+ *   projected: d_reproj = float32(z), (u', v') = float32 of the projection.
+ *   dist = sqrt((u' - x)^2 + (v' - y)^2) in fp64 on the float32 values; rel = |d_reproj - d_ref| / d_ref in float32.
+ *   Consistent iff d_ref is finite and > 0, dist < pixel_thresh and rel < float32(depth_thresh). (numpy compares its
+ *   float32 arrays with the Python thresholds in float32; so does min_confidence below.)
+ *   Stated deviation: cv2.remap additionally quantises the fractional sample position to 1/32 pixel and blends with
+ *   its own rounding; here the weights are the float32 fractions themselves.
+ * Per pixel: geo_sum = consistent sources; fused = float32((float32 sum of the consistent d_reproj in source order,
+ *   then + d_ref) / (geo_sum + 1), the division in fp64); geo = geo_sum >= min_consistent_views; conf = confidence >
+ *   float32(min_confidence); joint = geo and conf; d_fused is 0 where joint is false.
+ * Outputs: d_fused[n_views][height][width] float32; d_mask, one byte per pixel: bit 0 geo, bit 1 conf, bit 2 joint;
+ * d_counts[n_views][4] int64 = { geo pixels, conf pixels, joint pixels (the view's point count), reprojection errors
+ * counted }: the reference's three ratios times height * width; d_err[n_views][3] float64 = { sum, min, max } of dist
+ * over every source with dist < pixel_thresh at a joint pixel (min = max = 0 without one). The sum is accumulated as
+ * llround(dist 2^24) in 64-bit integers, hence pixel_thresh <= 1024. Everything is byte-identical from launch to launch.
+ * Workspace: 24 bytes per view. n_views == 0 returns GTSFM_OK and touches nothing; height or width == 0 zeroes d_counts
+ * and d_err; neither launches a kernel. A negative size, n_views > 65535, height * width >= 2^31 - 256, a threshold
+ * that is not a number, pixel_thresh outside [0, 1024] or a NULL required pointer: GTSFM_ERR_ARG; a short workspace:
+ * GTSFM_ERR_CAPACITY. */
+size_t gtsfm_mvs_fuse_depth_workspace_bytes(int n_views, int height, int width);
+
+int gtsfm_mvs_fuse_depth(const float* d_depth, const float* d_confidence, int n_views, int height, int width,
+                         const double* d_wRc, const double* d_wtc, const double* d_intrinsics, const int* d_src_views,
+                         int n_src, double pixel_thresh, double depth_thresh, double min_confidence,
+                         int min_consistent_views, void* d_workspace, size_t workspace_bytes, float* d_fused,
+                         uint8_t* d_mask, long long* d_counts, double* d_err, void* stream);
+
+/* The point cloud of the joint pixels: gtsfm/densify/mvs_patchmatchnet.py:325-357 (per view a boolean gather, a
+ * back-projection and a colour cast, then two concatenations on the host).
+ * A pixel is a point iff bit 2 of d_mask is set. d_view_offset[n_views + 1] int64 is the exclusive scan of the per-view
+ * point counts, taken on the device. Point k of view r, in row-major pixel order, goes to row d_view_offset[r] + k:
+ * views ascending, then row-major, the reference's concatenation order. d_points[capacity][3] float64 = wRc_r X_r +
+ * wtc_r with X_r from d_fused as above; d_colors[capacity][3] uint8 from d_images[n_images][image_height][image_width]
+ * [3] uint8, image d_view_image[r] (NULL = r; an index outside [0, n_images) gives black), pixel (x, y): the reference's
+ * ((float32(c) / 255) * 255).astype(uint8), evaluated in float32 and truncated (with a correctly rounded division that
+ * is c itself for all 256 values; the rule is evaluated all the same).
+ * image_height >= height and image_width >= width: the maps cover the top-left corner of the image, the reference's
+ * crop to multiples of 8. Rows at or past capacity are not written; d_view_offset[n_views] is the full count either
+ * way, so capacity == 0 only counts. Workspace: 12 bytes per 256 pixels of every view and 8 per view. An empty shape
+ * zeroes d_view_offset and launches no kernel; errors as for gtsfm_mvs_fuse_depth, and for an image smaller than the
+ * maps. */
+size_t gtsfm_mvs_gather_points_workspace_bytes(int n_views, int height, int width);
+
+int gtsfm_mvs_gather_points(const float* d_fused, const uint8_t* d_mask, int n_views, int height, int width,
+                            const double* d_wRc, const double* d_wtc, const double* d_intrinsics,
+                            const uint8_t* d_images, const int* d_view_image, int n_images, int image_height,
+                            int image_width, long long capacity, void* d_workspace, size_t workspace_bytes,
+                            double* d_points, uint8_t* d_colors, long long* d_view_offset, void* stream);
+
+/* The statistics behind the voxel size: gtsfm/densify/mvs_utils.py:148-190 estimate_voxel_scales and
+ * estimate_minimum_voxel_size (gtsfm/utils/ellipsoid.py center_point_cloud and get_right_singular_vectors).
+ * d_stats[18] float64 = { mean[3], scatter[9] (row-major, sum of the outer products of the centred points divided by
+ * n_points - 1; all 0 for n_points < 2), min bound[3], max bound[3] }. Two passes in fp64 with a fixed grid of
+ * workgroups and fixed-order sums: the same bytes from launch to launch. The voxel size is 0.02 sqrt(smallest
+ * eigenvalue of the scatter), taken by the caller. n_points == 0 zeroes d_stats and launches no kernel. Workspace: at
+ * most 72 KiB. n_points < 0 or a NULL pointer: GTSFM_ERR_ARG; a short workspace: GTSFM_ERR_CAPACITY. */
+size_t gtsfm_mvs_voxel_stats_workspace_bytes(long long n_points);
+
+int gtsfm_mvs_voxel_stats(const double* d_points, long long n_points, void* d_workspace, size_t workspace_bytes,
+                          double* d_stats, void* stream);
+
+/* Voxel downsampling: gtsfm/densify/mvs_utils.py:193-221 downsample_point_cloud (Open3D voxel_down_sample).
+ * gtsfm_mvs_voxel_keys: per axis the voxel index floor((p - (min_bound - voxel_size / 2)) / voxel_size), Open3D's
+ * rule, with min_bound read from the d_stats of gtsfm_mvs_voxel_stats; clamped to [0, 2^21 - 1] and packed as
+ * x << 42 | y << 21 | z into d_keys[n_points] int64. voxel_size must be > 0 (a size <= 0 means "return the cloud
+ * unchanged", the caller's business).
+ * The caller orders the keys with a stable sort and passes the sorted keys and the permutation (int64 indices into the
+ * input). gtsfm_mvs_voxel_downsample: one output row per distinct key, in ascending key order (Open3D's own order is
+ * that of its hash map and unspecified): d_out_points = the mean of the voxel's points, summed in fp64 in sorted order
+ * (ascending input index within a voxel); d_out_colors = the mean of the 0-255 values, truncated to uint8 (integer sum,
+ * integer division); d_out_keys, d_out_count (points per voxel); d_n_voxels[1] the number of rows. Every output array
+ * has n_points rows, zero past the voxel count. n_points == 0 zeroes d_n_voxels and launches no kernel. An extent of
+ * 2^21 voxels or more along an axis is the caller's to refuse (gtsfm_amd.densify.mvs_utils does): the clamp would
+ * merge everything past it into the last voxel, whose one lane would then add all those points. Workspace: 8 bytes
+ * per point and 12 per 256 points. A negative size or a NULL pointer: GTSFM_ERR_ARG; a short workspace: GTSFM_ERR_CAPACITY. */
+int gtsfm_mvs_voxel_keys(const double* d_points, long long n_points, const double* d_stats, double voxel_size,
+                         long long* d_keys, void* stream);
+
+size_t gtsfm_mvs_voxel_downsample_workspace_bytes(long long n_points);
+
+int gtsfm_mvs_voxel_downsample(const double* d_points, const uint8_t* d_colors, const long long* d_sorted_keys,
+                               const long long* d_perm, long long n_points, void* d_workspace, size_t workspace_bytes,
+                               double* d_out_points, uint8_t* d_out_colors, long long* d_out_keys, int* d_out_count,
+                               long long* d_n_voxels, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,212 @@
+"""CPU: pins the restatement of the dense-MVS geometry (tests/mvs_ref.py) to hand-derived answers, checks the host
+utilities of gtsfm_amd.densify and the binding, and asserts the conditions of the scene the GPU tests rely on."""
+import math
+
+import numpy as np
+import pytest
+
+from tests import mvs_ref as M
+
+
+def test_piecewise_gaussian_known_values():
+    from gtsfm_amd.densify import mvs_utils
+
+    for fn in (mvs_utils.piecewise_gaussian, lambda t: float(M.piecewise_gaussian(t))):
+        assert fn(5.0) == 1.0
+        assert fn(4.0) == pytest.approx(math.exp(-0.5), rel=1e-15)
+        assert fn(15.0) == pytest.approx(math.exp(-0.5), rel=1e-15)
+
+
+def test_angle_above_the_midpoint_of_a_baseline():
+    """Cameras at (-b, 0, 0) and (b, 0, 0), the point at height h above the midpoint: the angle is 2 atan(b / h)."""
+    from gtsfm_amd.densify import mvs_utils
+
+    for b, h in ((1.0, 10.0), (0.5, 3.0), (2.0, 2.0)):
+        want = math.degrees(2 * math.atan(b / h))
+        c1, c2, X = np.array([-b, 0, 0.0]), np.array([b, 0, 0.0]), np.array([0, 0, h])
+        assert float(M.triangulation_angle_deg(c1, c2, X)) == pytest.approx(want, rel=1e-13)
+        assert mvs_utils.calculate_triangulation_angle_in_degrees(c1, c2, X) == pytest.approx(want, rel=1e-13)
+        assert mvs_utils.calculate_triangulation_angles_in_degrees(c1, c2, np.stack([X, X]))[1] == \
+            pytest.approx(want, rel=1e-13)
+
+
+def test_percentile_equals_numpy():
+    rng = np.random.default_rng(0)
+    for n in (1, 2, 3, 7, 100, 101, 1000, 4097):
+        v = rng.normal(5.0, 2.0, n)
+        for q in (1, 99):
+            assert M.percentile(v, q / 100.0) == pytest.approx(np.percentile(v, q), rel=1e-14)
+
+
+def test_fixed_point_score_against_the_float_sum():
+    s = M.make_scene()
+    v = M.select_views(s.offsets, s.img, s.point, s.track_keep, s.inlier, s.wRc, s.wtc, s.cam_keep)
+    assert v.terms.sum() > 200
+    assert np.all(np.abs(v.scores / M.SCORE_SCALE - v.scores_float) <= v.terms * 2.0 ** -40)
+    np.testing.assert_array_equal(v.scores, v.scores.T)
+    assert v.img_to_pm.tolist() == [0, 1, 2, -1, 3, 4, 5] and v.pm_to_img.tolist() == [0, 1, 2, 4, 5, 6]
+
+
+def test_source_view_ties_go_to_the_lower_index():
+    scores = np.array([[0, 3, 3, 0], [3, 0, 0, 0], [3, 0, 0, 9], [0, 0, 9, 0]])
+    assert M.source_views(scores, 5).tolist() == [[1, 2, 3], [0, 2, 3], [3, 0, 1], [2, 0, 1]]
+    assert M.source_views(scores, 2).tolist() == [[1], [0], [3], [2]]
+
+
+def _plane_pair(W=40, H=24, shift=0.5, Z=8.0):
+    wRc = np.tile(np.eye(3), (2, 1, 1))
+    wtc = np.array([[0.0, 0, 0], [shift, 0, 0]])
+    intr = np.tile(np.array([50.0, (W - 1) / 2.0, (H - 1) / 2.0]), (2, 1))
+    depth = np.full((2, H, W), Z, np.float32)
+    return depth, wRc, wtc, intr
+
+
+def test_fronto_parallel_plane_reprojects_onto_itself():
+    """Identical cameras translated along x, a plane at depth Z: the source sample is at x - f shift / Z, the source
+    depth there is Z wherever the four taps lie inside, and the point reprojects onto its own pixel."""
+    depth, wRc, wtc, intr = _plane_pair()
+    H, W = depth.shape[1:]
+    dist, rel, d_rep, us, vs = M.reproject(depth, wRc, wtc, intr, 0, 1)
+    x = np.arange(W)[None, :] - 50.0 * 0.5 / 8.0
+    np.testing.assert_allclose(us, np.broadcast_to(x, (H, W)), atol=1e-5)
+    inside = (us >= 0) & (us <= W - 1) & (vs >= 0) & (vs <= H - 1)
+    assert inside.sum() > 0.8 * H * W
+    assert np.all(dist[inside] <= 1e-5) and np.all(rel[inside] <= 1e-6)
+    assert np.all(np.abs(d_rep[inside] - 8.0) <= 8e-6)
+    border = (us < 0) & (us > -1)  # blends with 0: fails
+    assert border.any() and np.all(rel[border] > 0.01)
+    assert np.all(d_rep[us <= -1] == 0)
+    f = M.fuse_depth(depth, np.full(depth.shape, 0.9, np.float32), wRc, wtc, intr, np.array([[1], [0]], np.int32))
+    assert np.array_equal((f.mask[0] & 4) != 0, inside)
+    assert np.all(np.abs(f.fused[0][inside] - 8.0) <= 8e-6) and np.all(f.fused[0][~inside] == 0)
+    assert f.counts[0].tolist() == [inside.sum(), H * W, inside.sum(), inside.sum()]
+
+
+def test_unusable_reference_depth_is_never_consistent():
+    depth, wRc, wtc, intr = _plane_pair()
+    depth[0, 5, 20], depth[0, 6, 20], depth[0, 7, 20], depth[0, 8, 20] = 0.0, np.nan, -2.0, np.inf
+    f = M.fuse_depth(depth, np.full(depth.shape, 0.9, np.float32), wRc, wtc, intr, np.array([[1], [0]], np.int32))
+    assert f.mask[0, 5:9, 20].tolist() == [2, 2, 2, 2] and np.all(f.fused[0, 5:9, 20] == 0)
+
+
+def test_colour_rule_for_all_values():
+    c = np.arange(256, dtype=np.uint8)
+    want = ((c.astype(np.float32) / 255) * 255).astype(np.uint8)
+    np.testing.assert_array_equal(M.color_rule(c), want)
+    # in float32 with a correctly rounded division the rule happens to return every value unchanged; the kernel still
+    # evaluates it, so that a change of either side shows
+    np.testing.assert_array_equal(want, c)
+
+
+def test_voxel_restatement_against_a_dictionary():
+    rng = np.random.default_rng(4)
+    pts = rng.uniform(-1, 1, (200, 3))
+    cols = rng.integers(0, 256, (200, 3)).astype(np.uint8)
+    voxel = 0.37
+    origin = pts.min(0) - voxel / 2
+    cells = {}
+    for p, c in zip(pts, cols):
+        cells.setdefault(tuple(np.floor((p - origin) / voxel).astype(int)), []).append((p, c))
+    out_p, out_c, keys, counts = M.voxel_downsample(pts, cols, pts.min(0), voxel)
+    assert len(out_p) == len(cells) < 200 and np.all(np.diff(keys) > 0) and counts.sum() == 200
+    for p, c, k, n in zip(out_p, out_c, keys, counts):
+        cell = cells[(int(k >> 42), int((k >> 21) & (2 ** 21 - 1)), int(k & (2 ** 21 - 1)))]
+        assert n == len(cell)
+        np.testing.assert_allclose(p, np.mean([q for q, _ in cell], axis=0), rtol=0, atol=1e-14)
+        np.testing.assert_array_equal(c, np.sum([q.astype(int) for _, q in cell], axis=0) // n)
+    stats = M.voxel_stats(pts)
+    np.testing.assert_allclose(stats[3:12].reshape(3, 3), np.cov(pts.T), rtol=1e-12)
+    assert M.voxel_size(stats, 200) == pytest.approx(0.02 * math.sqrt(np.linalg.eigvalsh(np.cov(pts.T))[0]), rel=1e-12)
+    assert M.voxel_size(M.voxel_stats(pts[:1]), 1) == 0.0
+
+
+def test_voxel_size_and_extent_on_the_host():
+    """The host halves of the voxel steps against the restatement: the size from the 18 statistics, and the refusal of
+    a cloud that spans more voxels along an axis than the 21-bit keys hold."""
+    from gtsfm_amd.densify import mvs_utils
+
+    rng = np.random.default_rng(5)
+    pts = rng.normal(0, 1, (300, 3)) * np.array([3.0, 1.0, 0.2])
+    stats = M.voxel_stats(pts)
+    assert mvs_utils.voxel_size_from_stats(stats, 300) == pytest.approx(M.voxel_size(stats, 300), rel=1e-15)
+    assert mvs_utils.voxel_size_from_stats(stats, 1) == 0.0
+    extent = (stats[15:18] - stats[12:15]).max()
+    mvs_utils.check_voxel_extent(stats, extent / 2 ** 20)
+    with pytest.raises(ValueError):
+        mvs_utils.check_voxel_extent(stats, extent / 2 ** 21)
+    keys = M.voxel_keys(pts, stats[12:15], extent / 2 ** 20)
+    assert (keys >> 42).max() < 2 ** 21 - 1  # no index reaches the clamp when the check passes
+
+
+def test_binding_carries_the_mvs_symbols():
+    from gtsfm_amd import native
+
+    L = native.lib()
+    names = [n for n in native.SIGNATURES if n.startswith("gtsfm_mvs_")]
+    assert len(names) == 11 and all(hasattr(L, n) for n in names)
+    assert L.gtsfm_mvs_select_views_workspace_bytes(300, 1000, 7) > 8 * 1000
+    assert L.gtsfm_mvs_select_views_workspace_bytes(0, 1000, 7) == 0
+    assert L.gtsfm_mvs_select_views_workspace_bytes(300, 1000, 50000) == 0
+    assert L.gtsfm_mvs_fuse_depth_workspace_bytes(6, 40, 72) >= 6 * 24
+    assert L.gtsfm_mvs_fuse_depth_workspace_bytes(0, 40, 72) == 0 == L.gtsfm_mvs_fuse_depth_workspace_bytes(6, -1, 72)
+    assert L.gtsfm_mvs_gather_points_workspace_bytes(6, 40, 72) > 0
+    assert 0 < L.gtsfm_mvs_voxel_stats_workspace_bytes(10 ** 9) <= 72 * 1024
+    assert L.gtsfm_mvs_voxel_downsample_workspace_bytes(1000) >= 8000
+    assert L.gtsfm_mvs_voxel_stats_workspace_bytes(0) == 0 == L.gtsfm_mvs_voxel_downsample_workspace_bytes(0)
+
+
+def test_densify_rejects_images_of_different_sizes():
+    from gtsfm_amd.bundle.bundle_adjustment import BaData
+    from gtsfm_amd.common import geometry as g
+    from gtsfm_amd.common.image import Image
+    from gtsfm_amd.densify.mvs_base import MVSBase, voxel_downsampling_metrics
+    from gtsfm_amd.densify.mvs_depth_fusion import MVSDepthFusion
+
+    cam = g.PinholeCameraCal3Bundler(g.Pose3(g.Rot3(np.eye(3)), np.zeros(3)), g.Cal3Bundler(50.0, 0, 0, 8, 8))
+    images = {0: Image(np.zeros((16, 16, 3), np.uint8)), 1: Image(np.zeros((16, 24, 3), np.uint8))}
+    mvs = MVSDepthFusion(lambda *a: None)
+    assert isinstance(mvs, MVSBase)
+    with pytest.raises(ValueError):
+        mvs.densify(images, BaData({0: cam, 1: cam}, []))
+    with pytest.raises(TypeError):
+        MVSBase()
+    assert voxel_downsampling_metrics(0.1, 10, 5)["compression ratio"] == pytest.approx(2.0)
+
+
+# ---------------------------------------------------------------- the conditions the GPU tests rely on
+@pytest.mark.parametrize("shape", [(72, 40), (136, 24)])
+def test_scene_conditions_hold_in_the_restatement(shape):
+    s = M.make_scene(*shape)
+    assert s.W % 64 != 0 and (s.H * s.W) % 256 != 0
+    v = M.select_views(s.offsets, s.img, s.point, s.track_keep, s.inlier, s.wRc, s.wtc, s.cam_keep)
+    nv = len(v.pm_to_img)
+    assert nv == 6 and v.src_views.shape == (6, 4) and not np.isnan(v.depth_range).any()
+    lens = np.diff(s.offsets)
+    assert len(lens) == 300 and lens.min() == 2 and lens.max() == 5
+    # every gap between rank V - 1 and rank V is 0 (the tie rule decides) or larger than the device slack of one
+    # unit per term on each of the two entries
+    for r in range(nv):
+        order = [c for c in v.src_views[r]] + sorted(set(range(nv)) - {r} - set(v.src_views[r].tolist()),
+                                                     key=lambda c: (-v.scores[r, c], c))
+        for a, b in zip(order[:-1], order[1:]):
+            gap = int(v.scores[r, a] - v.scores[r, b])
+            assert gap == 0 or gap > v.terms[r, a] + v.terms[r, b], (r, a, b, gap)
+    wRc, wtc, intr = M.valid_cameras(s)
+    f = M.fuse_depth(s.depth, s.conf, wRc, wtc, intr, v.src_views)
+    b = M.band(s, f)
+    print("band margins", M.band_margins(s), "band pixels per view", b.reshape(nv, -1).sum(1).tolist(),
+          "joint per view", f.counts[:, 2].tolist())
+    assert np.all(b.reshape(nv, -1).mean(1) <= 0.01)
+    assert f.counts[s.dead_view, 2] == 0 and 0 < s.dead_view < nv - 1  # a zero count inside the scan
+    assert np.all(np.delete(f.counts[:, 2], s.dead_view) > 0.1 * s.H * s.W)
+    assert f.counts[:, 3].sum() > f.counts[:, 2].sum()
+    # one source with many samples outside the map: the last camera looks to the side
+    outside = [(np.isfinite(f.dist[r, k]) & (f.rel[r, k] > 0.5)).mean() for r in range(nv) for k in range(4)
+               if v.src_views[r, k] == nv - 1]
+    assert outside and max(outside) > 0.2
+    pts, cols, off = M.gather_points(f.fused, f.mask, wRc, wtc, intr, s.images, v.pm_to_img)
+    assert off[-1] == f.counts[:, 2].sum() == len(pts) and off[s.dead_view] == off[s.dead_view + 1]
+    # the fused points lie on the surface: the plane or the sphere, within the 1 % depth threshold
+    on_plane = np.abs(pts[:, 2] - M.PLANE_Z)
+    on_sphere = np.abs(np.linalg.norm(pts - M.SPHERE_C, axis=1) - M.SPHERE_R)
+    assert np.mean(np.minimum(on_plane, on_sphere) < 0.01 * 12.0) > 0.97
