@@ -490,7 +490,9 @@ __global__ __launch_bounds__(MV_BLOCK) void fu_fuse_kernel(FuArgs a) {
             e_max = dist > e_max ? dist : e_max;
         }
     }
-    const bool geo = in && geo_sum >= a.min_views;
+    // ok: with min_views <= 0 a pixel without a usable depth would pass with (0 + d_ref) / 1 as its fused depth, and a
+    // NaN point would reach the cloud. With min_views >= 1 its geo_sum of 0 fails either way.
+    const bool geo = ok && geo_sum >= a.min_views;
     const bool cok = in && cf > a.min_conf;
     const bool joint = geo && cok;
     if (in) {

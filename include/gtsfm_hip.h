@@ -893,8 +893,11 @@ int gtsfm_mvs_select_views(const int* d_track_offsets, const int* d_track_img, l
  *   Stated deviation: cv2.remap additionally quantises the fractional sample position to 1/32 pixel and blends with
  *   its own rounding; here the weights are the float32 fractions themselves.
  * Per pixel: geo_sum = consistent sources; fused = float32((float32 sum of the consistent d_reproj in source order,
- *   then + d_ref) / (geo_sum + 1), the division in fp64); geo = geo_sum >= min_consistent_views; conf = confidence >
- *   float32(min_confidence); joint = geo and conf; d_fused is 0 where joint is false.
+ *   then + d_ref) / (geo_sum + 1), the division in fp64); geo = d_ref finite and > 0 and geo_sum >=
+ *   min_consistent_views; conf = confidence > float32(min_confidence); joint = geo and conf; d_fused is 0 where joint is
+ *   false. Stated deviation: the reference has no test of d_ref in geo. It changes nothing for min_consistent_views
+ *   >= 1, where such a pixel has geo_sum = 0; for min_consistent_views <= 0 the reference passes (0 + d_ref) / 1 on as
+ *   the fused depth, a NaN or a point at or behind the camera, and here the pixel is dropped.
  * Outputs: d_fused[n_views][height][width] float32; d_mask, one byte per pixel: bit 0 geo, bit 1 conf, bit 2 joint;
  * d_counts[n_views][4] int64 = { geo pixels, conf pixels, joint pixels (the view's point count), reprojection errors
  * counted }: the reference's three ratios times height * width; d_err[n_views][3] float64 = { sum, min, max } of dist

@@ -210,3 +210,134 @@ def test_scene_conditions_hold_in_the_restatement(shape):
     on_plane = np.abs(pts[:, 2] - M.PLANE_Z)
     on_sphere = np.abs(np.linalg.norm(pts - M.SPHERE_C, axis=1) - M.SPHERE_R)
     assert np.mean(np.minimum(on_plane, on_sphere) < 0.01 * 12.0) > 0.97
+
+
+# ---------------------------------------------------------------- the rules and scenes of tests/test_mvs_edges_gpu.py
+def test_gather_view_without_an_image_is_black():
+    """Two views of 2 x 2 at the origin with f = 1 and the principal point at pixel (0, 0): pixel (x, y) at depth 2 is
+    the point (2 x, 2 y, 2). View 0 takes its colours from image 1, cropped from the top-left corner of a 3 x 3 image;
+    views whose image index is -1 or past the last image are black and still give their points."""
+    fused = np.full((2, 2, 2), 2.0, np.float32)
+    mask = np.array([[[4, 3], [0, 7]], [[0, 4], [4, 1]]], np.uint8)
+    wRc, wtc, intr = np.tile(np.eye(3), (2, 1, 1)), np.zeros((2, 3)), np.tile(np.array([1.0, 0.0, 0.0]), (2, 1))
+    images = np.arange(2 * 3 * 3 * 3, dtype=np.uint8).reshape(2, 3, 3, 3)
+    for missing in (-1, 2, 5000):
+        pts, cols, off = M.gather_points(fused, mask, wRc, wtc, intr, images, np.array([1, missing]))
+        assert off.tolist() == [0, 2, 4]
+        assert pts.tolist() == [[0, 0, 2], [2, 2, 2], [2, 0, 2], [0, 2, 2]]
+        assert cols.tolist() == [images[1, 0, 0].tolist(), images[1, 1, 1].tolist(), [0, 0, 0], [0, 0, 0]]
+
+
+def test_percentile_edge_lists_equal_numpy():
+    lists = M.percentile_edge_lists()
+    assert len(lists) == 5 * len(M.PERCENTILE_LENGTHS)
+    for (kind, n), v in lists.items():
+        assert len(v) == n and np.isfinite(v).all()
+        for q in (1, 99):
+            assert M.percentile(v, q / 100.0) == pytest.approx(np.percentile(v, q, method="linear"), rel=1e-14), (kind, n)
+    # the lists are what they claim to be
+    bits = {k: v.view(np.uint64) for k, v in lists.items()}
+    assert np.all(lists["negative", 1025] < 0) and np.signbit(lists["mixed", 2]).tolist() == [True, False]
+    assert lists["mixed", 2].tolist() == [0.0, 0.0] and (lists["mixed", 1025] < 0).any() and (lists["mixed", 1025] > 0).any()
+    assert len(np.unique(bits["low_byte", 1025] >> np.uint64(8))) == 1 and len(np.unique(bits["low_byte", 1025])) > 200
+    assert len(np.unique(bits["sign_exponent", 1025] << np.uint64(12))) == 1
+    assert len(np.unique(bits["sign_exponent", 1025] >> np.uint64(52))) > 60
+
+
+def test_no_required_view_still_needs_a_depth_and_sources_count_as_listed():
+    """The plane pair again. With min_views = 0 every pixel with a usable depth is geometric, with its own depth as the
+    fused one where no source agrees; a pixel whose depth is 0, NaN, negative or infinite is not, so no such depth
+    reaches the cloud (the reference's filter would pass (0 + d_ref) / 1 on). A source listed twice counts twice, an
+    entry of -1 or n_views is skipped, and a row without a source has no geometric pixel for min_views >= 1."""
+    depth, wRc, wtc, intr = _plane_pair()
+    depth[0, 5, 20], depth[0, 6, 20], depth[0, 7, 20], depth[0, 8, 20] = 0.0, np.nan, -2.0, np.inf
+    conf = np.full(depth.shape, 0.9, np.float32)
+    f = M.fuse_depth(depth, conf, wRc, wtc, intr, np.array([[1], [0]], np.int32), min_views=0)
+    assert f.mask[0, 5:9, 20].tolist() == [2, 2, 2, 2] and np.all(f.fused[0, 5:9, 20] == 0)
+    usable = np.ones(depth.shape[1:], bool)
+    usable[5:9, 20] = False
+    assert np.all(f.mask[0][usable] == 7) and np.all(np.abs(f.fused[0][usable] - 8.0) <= 8e-6)
+    one = M.fuse_depth(depth, conf, wRc, wtc, intr, np.array([[1], [0]], np.int32))
+    assert np.all(f.fused[0, :, 0] == 8.0) and not (one.mask[0, :, 0] & 1).any()  # outside the source: d_ref itself
+    pts, _, off = M.gather_points(f.fused, f.mask, wRc, wtc, intr, np.zeros(depth.shape + (3,), np.uint8))
+    assert np.isfinite(pts).all() and off[1] == usable.sum()
+    inside = (one.mask[0] & 1) != 0
+    for row, min_views, want in (([1, 1], 2, inside), ([1, -1], 2, ~usable & usable), ([1, 2], 2, ~usable & usable),
+                                 ([1, 2], 1, inside), ([-1, -1], 1, ~usable & usable), ([-1, 2], 0, usable)):
+        g = M.fuse_depth(depth, conf, wRc, wtc, intr, np.array([row, [0, 0]], np.int32), min_views=min_views)
+        assert np.array_equal((g.mask[0] & 1) != 0, want), (row, min_views)
+    twice = M.fuse_depth(depth, conf, wRc, wtc, intr, np.array([[1, 1], [0, 0]], np.int32))
+    assert twice.counts[0, 3] == 2 * one.counts[0, 3] and twice.err[0, 0] == 2 * one.err[0, 0]
+    np.testing.assert_allclose(twice.fused[0][inside], one.fused[0][inside], rtol=3e-7)  # (2 d' + d) / 3 against (d' + d) / 2
+
+
+@pytest.mark.parametrize("name", list(M.FUSION_PARAMS))
+def test_unequal_scene_conditions_hold_in_the_restatement(name):
+    """The conditions tests/test_mvs_edges_gpu.py relies on, for every parameter set it runs: distinct cameras, at
+    most 1 % of each view in the band of the thresholds in use (margins from the largest f), and joint as well as
+    non-joint pixels in every view but the dead one, so that neither an all-pass nor an all-fail kernel agrees."""
+    params = M.FUSION_PARAMS[name]
+    s = M.make_scene(72, 40, **M.UNEQUAL)
+    wRc, wtc, intr = M.valid_cameras(s)
+    nv = len(intr)
+    f0 = M.FOCAL_PER_WIDTH * 72
+    assert len(np.unique(intr[:, 0])) == nv and intr[:, 0].min() < 0.88 * f0 and intr[:, 0].max() > 1.12 * f0
+    shift = intr[:, 1:] - np.array([35.5, 19.5])
+    assert len(np.unique(shift.round(3), axis=0)) == nv and np.abs(shift[:, 0]).max() > 4 and np.abs(shift[:, 1]).max() > 2
+    half = nv // 2  # neither equal nor mirrored about the middle camera
+    assert np.abs(shift[:half] - shift[:-half - 1:-1]).max(1).min() > 0.5
+    assert np.abs(shift[:half] + shift[:-half - 1:-1]).max(1).min() > 0.5
+    assert M.band_margins(s)[0] > 2.0 ** -16 + f0 * 1e-6  # the margin does scale with f
+    v = M.select_views(s.offsets, s.img, s.point, s.track_keep, s.inlier, s.wRc, s.wtc, s.cam_keep)
+    assert v.src_views.shape == (nv, 4)
+    f = M.fuse_depth(s.depth, s.conf, wRc, wtc, intr, v.src_views, **params)
+    b = M.band(s, f, **M.band_thresholds(params))
+    joint = f.counts[:, 2]
+    print(name, "band margins", M.band_margins(s), "band pixels per view", b.reshape(nv, -1).sum(1).tolist(),
+          "joint per view", joint.tolist())
+    assert np.all(b.reshape(nv, -1).mean(1) <= 0.01)
+    live = np.delete(np.arange(nv), s.dead_view)
+    assert joint[s.dead_view] == 0 and np.all(joint[live] > 0.1 * s.H * s.W) and np.all(joint[live] < 0.6 * s.H * s.W)
+    if params.get("min_views", 1) == 0:  # every usable depth is geometric; the nine unusable ones per view are not
+        assert np.all(f.counts[:, 0] == (np.isfinite(s.depth) & (s.depth > 0)).reshape(nv, -1).sum(1))
+        assert np.all(f.counts[:, 0] < s.H * s.W)
+    pts, _, off = M.gather_points(f.fused, f.mask, wRc, wtc, intr, s.images, v.pm_to_img)
+    assert np.isfinite(pts).all() and off[-1] == joint.sum()
+
+
+def test_ragged_source_rows_in_the_restatement():
+    s = M.make_scene(72, 40, **M.UNEQUAL)
+    wRc, wtc, intr = M.valid_cameras(s)
+    f = M.fuse_depth(s.depth, s.conf, wRc, wtc, intr, M.RAGGED_SRC)
+    assert M.RAGGED_SRC.shape == (6, 4) and (M.RAGGED_SRC == 6).any()
+    assert np.all(M.band(s, f).reshape(6, -1).mean(1) <= 0.01)
+    assert f.counts[1].tolist()[0::2] == [0, 0] and f.counts[1, 3] == 0
+    assert np.all(f.counts[[0, 2, 3, 5], 2] > 0.1 * s.H * s.W)
+    single = M.fuse_depth(s.depth, s.conf, wRc, wtc, intr, np.array([[-1]] * 5 + [[3]], np.int32))
+    assert f.counts[5, 3] == 3 * single.counts[5, 3] and np.array_equal(f.mask[5], single.mask[5])
+    two = M.fuse_depth(s.depth, s.conf, wRc, wtc, intr, M.RAGGED_SRC, min_views=2)
+    assert not two.counts[1, 0] and 0 < two.counts[0, 0] < f.counts[0, 0] and two.counts[5, 0] == f.counts[5, 0]
+
+
+def test_behind_scene_conditions_hold_in_the_restatement():
+    s = M.make_behind_scene()
+    x, y = np.meshgrid(np.arange(72.0), np.arange(40.0))
+    xs = M._transfer(s.wRc[0], s.wtc[0], s.intr[0], s.wRc[1], s.wtc[1], x, y, s.depth[0].astype(np.float64))
+    assert (xs[2] < 0).mean() > 0.2 and (xs[2] == 0).sum() == 5
+    assert xs[0][20, 36] == 0 and xs[1][20, 36] == 0 and xs[2][20, 36] < -0.4  # on the principal ray, behind
+    _, _, _, us, vs = M.reproject(s.depth, s.wRc, s.wtc, s.intr, 0, 1)
+    assert (us[20, 36], vs[20, 36]) == (33.5, 21.5)
+    inside = (us > -1) & (us < 72) & (vs > -1) & (vs < 40)
+    assert (inside & (xs[2] < 0)).sum() > 20  # behind the camera and still inside its map: sampled all the same
+    for x0, y0 in M.BEHIND_PIXELS["nan_inf"]:
+        assert np.isnan(us[y0, x0]) and np.isinf(vs[y0, x0])
+    for x0, y0 in M.BEHIND_PIXELS["inf_nan"]:
+        assert np.isinf(us[y0, x0]) and np.isnan(vs[y0, x0])
+    for x0, y0 in M.BEHIND_PIXELS["inf_inf"]:
+        assert np.isinf(us[y0, x0]) and np.isinf(vs[y0, x0])
+    src = np.array([[1, 2], [0, 2], [0, 1]], np.int32)
+    f = M.fuse_depth(s.depth, s.conf, s.wRc, s.wtc, s.intr, src)
+    assert np.all(M.band(s, f).reshape(3, -1).mean(1) <= 0.01)
+    assert np.all(f.counts[:, 2] > 0.1 * 72 * 40) and np.all(f.counts[:, 2] < 0.5 * 72 * 40)
+    alone = M.fuse_depth(s.depth, s.conf, s.wRc, s.wtc, s.intr, np.array([[1], [0], [-1]], np.int32))
+    assert not (alone.mask[0][xs[2] <= 0] & 1).any() and alone.counts[0, 0] > 20  # nothing behind B agrees with it
