@@ -30,8 +30,10 @@ import torch.nn.functional as F
 _ENC = [("conv1a", "conv1b"), ("conv2a", "conv2b"), ("conv3a", "conv3b"), ("conv4a", "conv4b")]
 
 
-def _t(sd: Dict[str, np.ndarray], name: str) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(sd[name]))
+def _t(sd: Dict[str, np.ndarray], name: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Parameter `name` as a tensor of `dtype` (the state dicts are float32: the default is no conversion)."""
+    t = torch.from_numpy(np.ascontiguousarray(sd[name]))
+    return t if dtype == torch.float32 else t.to(dtype)
 
 
 def _conv(x, sd, name, relu=True):
@@ -101,60 +103,73 @@ def superpoint(gray: np.ndarray, sd: Dict[str, np.ndarray], max_keypoints: int =
 
 
 def _mlp(x, sd, prefix, n, bn=True):
-    """Conv1d stack of superglue.py:50-58: conv (+ BatchNorm eval) + ReLU except after the last conv."""
+    """Conv1d stack of superglue.py:50-58: conv (+ BatchNorm eval) + ReLU except after the last conv. The
+    parameters follow x's dtype."""
+    dt = x.dtype
     for i in range(n):
         j = 3 * i if bn else 2 * i
-        x = F.conv1d(x, _t(sd, f"{prefix}.{j}.weight"), _t(sd, f"{prefix}.{j}.bias"))
+        x = F.conv1d(x, _t(sd, f"{prefix}.{j}.weight", dt), _t(sd, f"{prefix}.{j}.bias", dt))
         if i < n - 1:
             if bn:
                 q = f"{prefix}.{j + 1}"
-                x = F.batch_norm(x, _t(sd, q + ".running_mean"), _t(sd, q + ".running_var"), _t(sd, q + ".weight"),
-                                 _t(sd, q + ".bias"), False, 0.0, 1e-5)
+                x = F.batch_norm(x, _t(sd, q + ".running_mean", dt), _t(sd, q + ".running_var", dt),
+                                 _t(sd, q + ".weight", dt), _t(sd, q + ".bias", dt), False, 0.0, 1e-5)
             x = F.relu(x)
     return x
 
 
 def _attn_layer(x, src, sd, p):
     b, c, n = x.shape
-    q, k, v = (F.conv1d(t, _t(sd, f"{p}.attn.proj.{i}.weight"), _t(sd, f"{p}.attn.proj.{i}.bias")).view(b, 64, 4, -1)
-               for i, t in enumerate((x, src, src)))
+    dt = x.dtype
+    q, k, v = (F.conv1d(t, _t(sd, f"{p}.attn.proj.{i}.weight", dt), _t(sd, f"{p}.attn.proj.{i}.bias", dt))
+               .view(b, 64, 4, -1) for i, t in enumerate((x, src, src)))
     s = torch.einsum("bdhn,bdhm->bhnm", q, k) / 64 ** 0.5
     msg = torch.einsum("bhnm,bdhm->bdhn", F.softmax(s, dim=-1), v).contiguous().view(b, c, -1)
-    msg = F.conv1d(msg, _t(sd, f"{p}.attn.merge.weight"), _t(sd, f"{p}.attn.merge.bias"))
+    msg = F.conv1d(msg, _t(sd, f"{p}.attn.merge.weight", dt), _t(sd, f"{p}.attn.merge.bias", dt))
     return _mlp(torch.cat([x, msg], 1), sd, f"{p}.mlp", 2)
 
 
 def superglue(kp0, kp1, d0, d1, s0, s1, hw0, hw1, sd: Dict[str, np.ndarray], sinkhorn_iterations: int = 20,
-              match_threshold: float = 0.2, n_layers: int = 18) -> Tuple[np.ndarray, np.ndarray]:
-    """matches0 (N0,) int64 (-1 = none) and matching_scores0 (N0,) of one pair; d0 (N0, 256), kp (N, 2) x, y."""
+              match_threshold: float = 0.2, n_layers: int = 18, return_log_assignment: bool = False,
+              dtype: torch.dtype = torch.float32):
+    """matches0 (N0,) int64 (-1 = none) and matching_scores0 (N0,) of one pair; d0 (N0, 256), kp (N, 2) x, y.
+    return_log_assignment: also the (N0 + 1, N1 + 1) log-assignment matrix (log_optimal_transport's output, dustbins
+    last). dtype: the precision the whole restatement runs in (inputs, parameters, Sinkhorn); the scores and the
+    matrix come back in it."""
+    np_dt = np.float64 if dtype == torch.float64 else np.float32
     if len(kp0) == 0 or len(kp1) == 0:
-        return np.full(len(kp0), -1, np.int64), np.zeros(len(kp0), np.float32)
+        out = np.full(len(kp0), -1, np.int64), np.zeros(len(kp0), np_dt)
+        return out + (np.zeros((0, 0), np_dt),) if return_log_assignment else out
     with torch.no_grad():
+        def tt(a):
+            return torch.from_numpy(np.asarray(a, np.float32)).to(dtype)
+
         def norm(kp, hw):
-            size = torch.tensor([float(hw[1]), float(hw[0])])[None]
-            return (torch.from_numpy(np.asarray(kp, np.float32)) - size / 2) / (size.max() * 0.7)
+            size = torch.tensor([float(hw[1]), float(hw[0])], dtype=dtype)[None]
+            return (tt(kp) - size / 2) / (size.max() * 0.7)
 
         def enc(kp, s, hw):
-            inp = torch.cat([norm(kp, hw).T[None], torch.from_numpy(np.asarray(s, np.float32))[None, None]], 1)
+            inp = torch.cat([norm(kp, hw).T[None], tt(s)[None, None]], 1)
             return _mlp(inp, sd, "kenc.encoder", 5)
 
-        x0 = torch.from_numpy(np.asarray(d0, np.float32)).T[None] + enc(kp0, s0, hw0)
-        x1 = torch.from_numpy(np.asarray(d1, np.float32)).T[None] + enc(kp1, s1, hw1)
+        x0 = tt(d0).T[None] + enc(kp0, s0, hw0)
+        x1 = tt(d1).T[None] + enc(kp1, s1, hw1)
         for layer in range(n_layers):
             p = f"gnn.layers.{layer}"
             src0, src1 = (x1, x0) if layer % 2 else (x0, x1)
             x0, x1 = x0 + _attn_layer(x0, src0, sd, p), x1 + _attn_layer(x1, src1, sd, p)
-        w, bias = _t(sd, "final_proj.weight"), _t(sd, "final_proj.bias")
+        w, bias = _t(sd, "final_proj.weight", dtype), _t(sd, "final_proj.bias", dtype)
         m0, m1 = F.conv1d(x0, w, bias), F.conv1d(x1, w, bias)
         scores = torch.einsum("bdn,bdm->bnm", m0, m1) / 256 ** 0.5
-        Z = log_optimal_transport(scores, _t(sd, "bin_score"), sinkhorn_iterations)
+        Z = log_optimal_transport(scores, _t(sd, "bin_score", dtype), sinkhorn_iterations)
         mx0, mx1 = Z[:, :-1, :-1].max(2), Z[:, :-1, :-1].max(1)
         i0, i1 = mx0.indices, mx1.indices
         mutual0 = torch.arange(i0.shape[1])[None] == i1.gather(1, i0)
-        ms0 = torch.where(mutual0, mx0.values.exp(), torch.zeros(()))
+        ms0 = torch.where(mutual0, mx0.values.exp(), torch.zeros((), dtype=dtype))
         valid0 = mutual0 & (ms0 > match_threshold)
         i0 = torch.where(valid0, i0, torch.full_like(i0, -1))
-    return i0[0].numpy().astype(np.int64), ms0[0].numpy()
+    out = i0[0].numpy().astype(np.int64), ms0[0].numpy()
+    return out + (Z[0].numpy(),) if return_log_assignment else out
 
 
 def log_optimal_transport(scores: torch.Tensor, alpha: torch.Tensor, iters: int) -> torch.Tensor:
