@@ -6,7 +6,8 @@ compute_filtered_reprojection_error) and gtsfm/densify/patchmatchnet_data.py:28-
 estimator is any callable `depth_estimator(images, proj_inputs, depth_range) -> (depth, confidence)` over device
 tensors, where images is (n_valid, H, W, 3) uint8 in pm_i order, proj_inputs the tuple (wRc (n_valid, 3, 3), wtc
 (n_valid, 3), intrinsics (n_valid, 3), src_views (n_valid, S) int32) and depth_range (n_valid, 2); it returns two
-(n_valid, H, W) float32 tensors. PatchmatchNet on torch-ROCm is one such callable and is not part of this module.
+(n_valid, H, W) float32 tensors. gtsfm_amd.densify.patchmatchnet.PatchmatchNetDepthEstimator is that callable on the HIP
+PatchmatchNet, and gtsfm_amd.densify.mvs_patchmatchnet.MVSPatchmatchNet the two together.
 
 Not built: the reference's resize of every image to the size of image 0 (all images must share one size: ValueError),
 the quantiles of the reprojection errors (count, mean, min and max are reported), .ply output, Dask.

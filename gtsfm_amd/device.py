@@ -1260,3 +1260,59 @@ def mvs_voxel_downsample(points: torch.Tensor, colors: torch.Tensor, stats: torc
                                       native.stream_handle(stream))
     native.check(rc, "gtsfm_mvs_voxel_downsample")
     return r
+
+
+@dataclass(eq=False)
+class PatchmatchNetResult:
+    """Outputs of patchmatchnet_depth, all on the device: depth and confidence (n, H, W) float32; with debug=True also
+    features = the channels-last maps of every view ((n, H/8, W/8, 64), (n, H/4, W/4, 32), (n, H/2, W/2, 16)) and
+    iter_depths = the depth after each of the five patchmatch iterations (two (n, H/8, W/8), two (n, H/4, W/4), one
+    (n, H/2, W/2)), else None."""
+
+    depth: torch.Tensor
+    confidence: torch.Tensor
+    features: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
+    iter_depths: Optional[Tuple[torch.Tensor, ...]] = None
+
+
+def patchmatchnet_depth(images: torch.Tensor, wRc: torch.Tensor, wtc: torch.Tensor, intrinsics: torch.Tensor,
+                        src_views: torch.Tensor, depth_range: torch.Tensor, weights: torch.Tensor,
+                        init_uniform: torch.Tensor, debug: bool = False,
+                        config: Optional[native.PatchmatchNetConfig] = None,
+                        stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None
+                        ) -> PatchmatchNetResult:
+    """PatchmatchNet depth and confidence of every view of a batch (gtsfm_patchmatchnet_batched): images (n, H, W, 3)
+    uint8 with H and W multiples of 8, cameras per view, src_views (n, S) int32 rows of the same batch, depth_range
+    (n, 2) float64, weights the packed blob (gtsfm_amd.densify.patchmatchnet.pack_patchmatchnet_weights), init_uniform
+    (n, 48, H/8, W/8) float32 in [0, 1). Nothing is copied to the host or synchronised."""
+    _check(images, "images", _U8, shape=(None, None, None, 3))
+    n, H, W = images.shape[:3]
+    assert _check_cameras(wRc, wtc, intrinsics, None) == n, f"{intrinsics.numel() // 3} cameras for {n} views"
+    _check(src_views, "src_views", _I32, shape=(n, None))
+    S = src_views.shape[1]
+    _check(depth_range, "depth_range", _F64, shape=(n, 2))
+    L = native.lib()
+    _check(weights, "weights", _F32, numel=L.gtsfm_patchmatchnet_weights_floats())
+    _check(init_uniform, "init_uniform", _F32, shape=(n, native.PATCHMATCHNET_INIT_BINS, H // 8, W // 8))
+    dev = images.device
+    r = PatchmatchNetResult(torch.empty((n, H, W), dtype=_F32, device=dev),
+                            torch.empty((n, H, W), dtype=_F32, device=dev))
+    feat = iters = None
+    if debug:
+        sizes = [(H // 8, W // 8, 64), (H // 4, W // 4, 32), (H // 2, W // 2, 16)]
+        feat = torch.empty(sum(n * h * w * c for h, w, c in sizes), dtype=_F32, device=dev)
+        iters = torch.empty(sum(n * h * w * k for (h, w, _), k in zip(sizes, (2, 2, 1))), dtype=_F32, device=dev)
+    ws = _take_workspace(L.gtsfm_patchmatchnet_workspace_bytes(n, S, H, W), dev, workspace, stream,
+                         f"gtsfm_patchmatchnet_batched: unsupported shape {n} views with {S} sources of {H} x {W}")
+    rc = L.gtsfm_patchmatchnet_batched(_ptr(images), n, H, W, _ptr(wRc), _ptr(wtc), _ptr(intrinsics), _ptr(src_views),
+                                       S, _ptr(depth_range), _ptr(weights), _ptr(init_uniform),
+                                       None if config is None else ctypes.addressof(config), _ptr(ws), ws.numel(),
+                                       _ptr(r.depth), _ptr(r.confidence), _ptr(feat), _ptr(iters),
+                                       native.stream_handle(stream))
+    native.check(rc, "gtsfm_patchmatchnet_batched")
+    if debug:
+        r.features = tuple(t.view(n, h, w, c) for t, (h, w, c) in
+                           zip(feat.split([n * h * w * c for h, w, c in sizes]), sizes))
+        maps = [s for s, k in zip(sizes, (2, 2, 1)) for _ in range(k)]
+        r.iter_depths = tuple(t.view(n, h, w) for t, (h, w, _) in zip(iters.split([n * h * w for h, w, _ in maps]), maps))
+    return r

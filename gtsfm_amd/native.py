@@ -77,6 +77,24 @@ BA_INPUT_STATS_FIELDS = ("components", "cameras_kept", "tracks_kept", "measureme
 MVS_VIEWS_STATS_FIELDS = ("valid_cameras", "source_views", "cameras_without_depth", "score_terms")
 MVS_FUSE_COUNT_FIELDS = ("geometric_pixels", "confidence_pixels", "joint_pixels", "reprojection_errors")
 MVS_SCORE_SCALE = 2.0 ** 40  # gtsfm_mvs_select_views' scores are integers in units of 2^-40
+PATCHMATCHNET_INIT_BINS = 48  # inverse-depth bins of the random initialisation (gtsfm_patchmatchnet_batched)
+
+
+class PatchmatchNetConfig(ctypes.Structure):
+    """gtsfm_patchmatchnet_config; the default is the reference's (the only one the library takes)."""
+
+    _fields_ = [("interval_scale", c_double * 3), ("propagation_range", c_int * 3), ("iterations", c_int * 3),
+                ("num_samples", c_int * 3), ("propagate_neighbors", c_int * 3), ("evaluate_neighbors", c_int * 3),
+                ("groups", c_int * 3)]
+
+    def __init__(self, interval_scale=(0.005, 0.0125, 0.025), propagation_range=(6, 4, 2), iterations=(1, 2, 2),
+                 num_samples=(8, 8, 16), propagate_neighbors=(0, 8, 16), evaluate_neighbors=(9, 9, 9),
+                 groups=(4, 8, 8)):
+        super().__init__((c_double * 3)(*interval_scale), (c_int * 3)(*propagation_range), (c_int * 3)(*iterations),
+                         (c_int * 3)(*num_samples), (c_int * 3)(*propagate_neighbors),
+                         (c_int * 3)(*evaluate_neighbors), (c_int * 3)(*groups))
+
+
 TRI_STATS_FIELDS = ("success", "cheirality_failure", "inliers_underconstrained", "poses_underconstrained",
                     "exceeds_reproj_thresh", "low_triangulation_angle", "inlier_measurements", "hypotheses")
 
@@ -237,6 +255,14 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p],
+    ),
+    "gtsfm_patchmatchnet_set_phase_events": (c_int, [c_void_p]),
+    "gtsfm_patchmatchnet_weights_floats": (c_size_t, []),
+    "gtsfm_patchmatchnet_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gtsfm_patchmatchnet_batched": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
 }
 

@@ -41,6 +41,8 @@
  *                              gtsfm/densify/mvs_patchmatchnet.py:201-437 filter_depth with
  *                              thirdparty/patchmatchnet/eval.py:11-125, gtsfm/densify/mvs_base.py:75-92 and
  *                              gtsfm/densify/mvs_utils.py:148-221 (everything around the depth network)
+ *   gtsfm_patchmatchnet_*   <- gtsfm/densify/mvs_patchmatchnet.py:95-175 (the model call of densify) and
+ *                              thirdparty/patchmatchnet/models/net.py, patchmatch.py, module.py (the network)
  */
 #ifndef GTSFM_HIP_H_
 #define GTSFM_HIP_H_
@@ -817,7 +819,7 @@ int gtsfm_assemble_ba_input(const int* d_track_offsets, const int* d_track_img, 
                             void* stream);
 
 /* ----------------------------------------------------------------------------------------------
- * Dense multi-view stereo around a depth estimator (gtsfm/densify/). The depth network is not part of this library:
+ * Dense multi-view stereo around a depth estimator (gtsfm/densify/). The depth network is gtsfm_patchmatchnet_* below;
  * these calls choose its inputs and turn its depth and confidence maps into a point cloud. GTSFM_HIP_ABI_VERSION stays
  * 407 with gtsfm_mvs_* added: new symbols only.
  *
@@ -972,6 +974,60 @@ int gtsfm_mvs_voxel_downsample(const double* d_points, const uint8_t* d_colors, 
                                const long long* d_perm, long long n_points, void* d_workspace, size_t workspace_bytes,
                                double* d_out_points, uint8_t* d_out_colors, long long* d_out_keys, int* d_out_count,
                                long long* d_n_voxels, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * PatchmatchNet: the depth network of the dense-MVS stage, eval mode, fp32, batched over reference views.
+ * Replaces the model call of MVSPatchmatchNet.densify (gtsfm/densify/mvs_patchmatchnet.py:95-175, BATCH_SIZE 1, one
+ * FeatureNet pass per (reference, source) use) and the network itself: thirdparty/patchmatchnet/models/net.py:15-330
+ * (FeatureNet, Refinement, PatchmatchNet.forward), patchmatch.py:19-983 (initialisation, propagation, evaluation, the
+ * three 1x1x1 nets) and module.py:134-213 (differentiable_warping, depth_regression); the per-stage projection
+ * matrices of gtsfm/densify/patchmatchnet_data.py:208-227 are formed inside. GTSFM_HIP_ABI_VERSION stays 407: new
+ * symbols only.
+ *
+ * Every view of the batch is a reference view once; its sources are d_src_views[view][n_src], rows of the same batch
+ * (an index outside [0, n_views) is skipped). Features are computed once per view.
+ * d_images [n_views][H][W][3] uint8 RGB; H and W multiples of 8, at least 16. Cameras as for gtsfm_mvs_*: d_wRc
+ * [n_views][9], d_wtc [n_views][3], d_intrinsics [n_views][3] = (f, u0, v0), float64; stage s uses the first two rows
+ * of K divided by 2^s, and src_proj ref_proj^-1 is formed in fp64 from the poses (no matrix inverse) and rounded to fp32
+ * once. d_depth_range [n_views][2] float64 = (min, max). d_init_uniform [n_views][48][H/8][W/8] float32 in [0, 1): the
+ * random initialisation's numbers (torch.rand in the reference), an input so that a run can be repeated.
+ * config: NULL, or the reference's constants (interval scales 0.005 / 0.0125 / 0.025, propagation ranges 6 / 4 / 2,
+ * iterations 1 / 2 / 2, samples 8 / 8 / 16, propagate neighbours 0 / 8 / 16, evaluate neighbours 9 / 9 / 9, groups
+ * 4 / 8 / 8, each indexed by stage - 1); anything else is GTSFM_ERR_ARG.
+ * Outputs: d_depth_out and d_confidence_out [n_views][H][W] float32 (refined_depth["stage_0"] and
+ * photometric_confidence). Optional, NULL = not wanted: d_features_out, the channels-last feature maps of every view,
+ * stage 3 [n][H/8][W/8][64], then stage 2 [n][H/4][W/4][32], then stage 1 [n][H/2][W/2][16]; d_iter_depth_out, the depth
+ * after each of the five patchmatch iterations: two [n][H/8][W/8] maps, two [n][H/4][W/4], one [n][H/2][W/2].
+ *
+ * d_weights: gtsfm_patchmatchnet_weights_floats() floats, BatchNorm (eps 1e-5) folded into the layer before it. A
+ * convolution is W[ky][kx][ci][co] followed by bias[co] (zeros where the layer has none); a 1x1x1 net with G groups is
+ * W0[G][16], b0[16], W1[16][8], b1[8], W2[8], b2[1]. In order: feature.conv0 .. conv10; output1, inner1, inner2,
+ * output2, output3; for stage 3, 2, 1: evaluation.pixel_wise_net (stage 3 only), evaluation.similarity_net, propa_conv
+ * (stages 3 and 2), eval_conv, feature_weight_net; upsample_net.conv0, conv1, conv2, deconv (+ bn; the transposed
+ * convolution's weight[ci][co][ky][kx] stored as W[ky][kx][ci][co]), conv3, res.
+ * Workspace: about 120 bytes per pixel of the batch plus 4 n_src bytes per stage-3 pixel; the query returns 0 for a
+ * shape the call refuses. A NULL required pointer or a refused shape: GTSFM_ERR_ARG; a short workspace:
+ * GTSFM_ERR_CAPACITY.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    double interval_scale[3];
+    int propagation_range[3], iterations[3], num_samples[3], propagate_neighbors[3], evaluate_neighbors[3], groups[3];
+} gtsfm_patchmatchnet_config;
+
+size_t gtsfm_patchmatchnet_weights_floats(void);
+
+size_t gtsfm_patchmatchnet_workspace_bytes(int n_views, int n_src, int height, int width);
+
+int gtsfm_patchmatchnet_batched(const uint8_t* d_images, int n_views, int height, int width, const double* d_wRc,
+                                const double* d_wtc, const double* d_intrinsics, const int* d_src_views, int n_src,
+                                const double* d_depth_range, const float* d_weights, const float* d_init_uniform,
+                                const gtsfm_patchmatchnet_config* config, void* d_workspace, size_t workspace_bytes,
+                                float* d_depth_out, float* d_confidence_out, float* d_features_out,
+                                float* d_iter_depth_out, void* stream);
+
+/* Measurement hook, as gtsfm_match_set_kernel_events: events[6] are hipEvent_t recorded on the call's stream before
+ * FeatureNet, before stage 3, stage 2, stage 1, Refinement, and at the end. NULL switches it off. Not thread-safe. */
+int gtsfm_patchmatchnet_set_phase_events(void* const* events);
 
 #ifdef __cplusplus
 }
