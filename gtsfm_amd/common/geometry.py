@@ -112,8 +112,16 @@ except ImportError:
 def calibration_params(cal) -> np.ndarray:
     """(f, u0, v0) of a Cal3Bundler; the device path requires k1 == k2 == 0 (true for every reference loader)."""
     if abs(cal.k1()) > 0 or abs(cal.k2()) > 0:
-        raise NotImplementedError("radial distortion is not supported on the MI355X verifier path")
+        raise NotImplementedError("radial distortion is not supported on the fixed-calibration MI355X paths (the "
+                                  "verifiers, triangulation, gtsfm_global_ba); bundle adjustment takes it with "
+                                  "BundleAdjustmentOptimizer(refine_calibration=True), through calibration_params5")
     return np.array([cal.fx(), cal.px(), cal.py()], dtype=np.float64)
+
+
+def calibration_params5(cal) -> np.ndarray:
+    """(f, k1, k2, u0, v0) of a Cal3Bundler, the argument order of its constructor and the row gtsfm_global_ba_calib
+    reads and writes."""
+    return np.array([cal.fx(), cal.k1(), cal.k2(), cal.px(), cal.py()], dtype=np.float64)
 
 
 def rotation_matrix(R) -> np.ndarray:

@@ -4,7 +4,9 @@
 // gtsfm/bundle/global_ba.py and gtsfm/common/gtsfm_data.py:389-427 (filter_landmarks), on GTSAM 4.2's
 // LevenbergMarquardtOptimizer. The factors, the priors, the retraction, the cheirality treatment and the LM schedule
 // are ba2.hip's, generalised from two cameras (camera 0 = identity) to N cameras with an arbitrary first camera; the
-// SO(3) / SE(3) helpers are se3.hpp's for both. Calibration is held fixed (k1 = k2 = 0), as ba2.hip:19-22 states.
+// SO(3) / SE(3) helpers are se3.hpp's for both. This entry point holds calibration fixed (k1 = k2 = 0), as
+// ba2.hip:19-22 states; gba_calib.hip is the same solver with Cal3Bundler (f, k1, k2) refined, per camera or shared, and
+// gba_shared.hpp holds what the two files have in common.
 //
 // What differs from ba2.hip is the linear solve. The 6C x 6C reduced camera system is never formed: each LM trial
 // eliminates the points (3 x 3 blocks, damped) and solves S dc = b by preconditioned conjugate gradients from a zero
@@ -27,13 +29,13 @@
 #pragma clang fp contract(off)
 
 #include "csr.hpp"
+#include "gba_shared.hpp"
 #include "lm.hpp"
 #include "reduce.hpp"
 #include "se3.hpp"
 
 namespace {
 
-constexpr double kPointPriorW = 100.0;  // PriorFactorPoint3 sigma 0.1
 constexpr int kLin = 20;       // doubles per measurement: Jx[12], Jp[6], b[2]
 constexpr int kCamBlock = 256;  // lanes of a camera-grouped workgroup
 constexpr int kVecBlock = 1024; // lanes of the single-workgroup vector kernels
@@ -43,50 +45,6 @@ constexpr int kSortChunksMax = 1024;
 enum { S_RR = 0, S_RZ = 1, S_BB = 2, S_OLDLIN = 3, S_NEWLIN = 4, S_NEWERR = 5, S_XI0 = 8, S_COUNT = 16 };
 // icnt[] slots (ints, device)
 enum { I_NPART = 0, I_NMOD = 1, I_T0 = 2, I_C0 = 3, I_NFAC = 4, I_NKEPT = 5, I_BAD = 6, I_COUNT = 8 };
-
-// Logmap(A^-1 B): the pose prior's residual at B for a prior at A (ba2.hip has A = identity)
-__device__ void pose_local(const Pose& A, const Pose& B, double* xi) {
-    Pose T;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            T.R[3 * i + j] = A.R[i] * B.R[j] + A.R[3 + i] * B.R[3 + j] + A.R[6 + i] * B.R[6 + j];
-    const double d[3] = {B.t[0] - A.t[0], B.t[1] - A.t[1], B.t[2] - A.t[2]};
-    mtv3(A.R, d, T.t);
-    pose_log(T, xi);
-}
-
-// inverse of a symmetric positive definite 6 x 6 (full storage) by Cholesky; false when it is not positive definite
-__device__ bool spd6_inverse(const double* S, double* Inv) {
-    double L[36];
-    for (int k = 0; k < 36; ++k) L[k] = S[k];
-    for (int j = 0; j < 6; ++j) {
-        double v = L[7 * j];
-        for (int k = 0; k < j; ++k) v -= L[6 * j + k] * L[6 * j + k];
-        if (!(v > 0.0) || !isfinite(v)) return false;
-        const double d = sqrt(v);
-        L[7 * j] = d;
-        for (int i = j + 1; i < 6; ++i) {
-            double w = L[6 * i + j];
-            for (int k = 0; k < j; ++k) w -= L[6 * i + k] * L[6 * j + k];
-            L[6 * i + j] = w / d;
-        }
-    }
-    for (int c = 0; c < 6; ++c) {
-        double s[6];
-        for (int i = 0; i < 6; ++i) {
-            double v = (i == c) ? 1.0 : 0.0;
-            for (int k = 0; k < i; ++k) v -= L[6 * i + k] * s[k];
-            s[i] = v / L[7 * i];
-        }
-        for (int i = 5; i >= 0; --i) {
-            double v = s[i];
-            for (int k = i + 1; k < 6; ++k) v -= L[6 * k + i] * s[k];
-            s[i] = v / L[7 * i];
-        }
-        for (int i = 0; i < 6; ++i) Inv[6 * i + c] = s[i];
-    }
-    return true;
-}
 
 struct GbaArgs {
     // inputs
@@ -218,20 +176,6 @@ __global__ void gba_setup_cams(GbaArgs a) {
     atomicAdd(&a.icnt[I_NMOD], 1);
     atomicMin(&a.icnt[I_C0], c);
 }
-
-// csr.hpp source: the factor measurements grouped by camera, perm[] their camera-major order
-struct GbaByCamera {
-    static constexpr int kKeys = 1;
-    const int* mtrack;
-    const int* img;
-    int* perm;
-    __device__ bool keys(long long m, int* k) const {
-        if (mtrack[m] < 0) return false;
-        k[0] = img[m];
-        return true;
-    }
-    __device__ void put(long long m, const int*, const size_t* slot) const { perm[slot[0]] = (int)m; }
-};
 
 // ------------------------------------------------------------------ nonlinear error of (X, P): per-track partials
 __device__ double track_error(const GbaArgs& a, const double* X, const double* p, int t, int b, int e) {
@@ -473,7 +417,7 @@ __global__ __launch_bounds__(kCamBlock) void gba_cam_build(GbaArgs a, double lam
         for (int r = 0; r < 6; ++r)
             for (int s = r; s < 6; ++s, ++n) S[6 * r + s] = S[6 * s + r] = H[6 * r + s] - v[n];
         for (int k = 0; k < 6; ++k) S[7 * k] += lambda;
-        if (!spd6_inverse(S, Inv)) {
+        if (!spd_inverse<6>(S, Inv)) {
             for (int k = 0; k < 36; ++k) Inv[k] = 0.0;
             a.icnt[I_BAD] = 1;
         }

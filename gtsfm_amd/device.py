@@ -849,6 +849,64 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
 
 
 @dataclass(eq=False)
+class GlobalBaCalibResult(GlobalBaResult):
+    """Outputs of global_ba_calib: GlobalBaResult's, with stats (12,) in the order of native.GBA_CALIB_STATS_FIELDS, plus
+    calib (n_img, 5) float64 = (f, k1, k2, u0, v0), refined for the modelled cameras."""
+
+    calib: torch.Tensor
+
+
+def global_ba_calib(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: torch.Tensor,
+                    point: torch.Tensor, track_valid: Optional[torch.Tensor], meas_valid: Optional[torch.Tensor],
+                    wRc: torch.Tensor, wtc: torch.Tensor, calib: torch.Tensor, cam_valid: Optional[torch.Tensor],
+                    robust: bool = False, measurement_sigma: float = 1.0, cam_pose3_prior_sigma: float = 0.1,
+                    shared_calib: bool = False, calibration_prior_sigma: float = 1e-5, max_iterations: int = 0,
+                    pcg_rel_tol: float = 1e-10, pcg_max_iter: int = 2000, reproj_error_thresh: float = float("inf"),
+                    n_tracks: Optional[int] = None, n_tracks_dev: Optional[torch.Tensor] = None,
+                    stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None,
+                    workspace_bytes: Optional[int] = None) -> GlobalBaCalibResult:
+    """global_ba with the Cal3Bundler calibration (f, k1, k2) refined, one variable per modelled camera or, with
+    shared_calib, one for all (gtsfm_global_ba_calib; semantics in include/gtsfm_hip.h).
+
+    The arguments are global_ba's, with calib (n_img, 5) float64 = (f, k1, k2, u0, v0) in place of intrinsics, and the
+    prior sigma of the calibration variables. Like global_ba the call synchronises the stream."""
+    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
+    _check(point, "point", _F64, min_numel=3 * T)
+    n_img = calib.numel() // 5
+    _check(wRc, "wRc", _F64, numel=9 * n_img)
+    _check(wtc, "wtc", _F64, numel=3 * n_img)
+    _check(calib, "calib", _F64, numel=5 * n_img)
+    _check(cam_valid, "cam_valid", _U8, numel=n_img, optional=True)
+    if track_valid is not None and track_valid.dtype == torch.bool:
+        track_valid = track_valid.to(torch.uint8)
+    _check(track_valid, "track_valid", _U8, min_numel=T, optional=True)
+    _check(meas_valid, "meas_valid", _U8, numel=n_meas, optional=True)
+    dev = track_offsets.device
+    wRc_out = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
+    wtc_out = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
+    calib_out = torch.empty((n_img, 5), dtype=torch.float64, device=dev)
+    point_out = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    track_keep = torch.empty(T, dtype=torch.uint8, device=dev)
+    cam_keep = torch.empty(n_img, dtype=torch.uint8, device=dev)
+    stats = torch.empty(12, dtype=torch.float64, device=dev)
+    L = native.lib()
+    ws = _take_workspace(L.gtsfm_global_ba_calib_workspace_bytes(T, n_meas, n_img), dev, workspace, stream,
+                         None if T == 0 or n_meas == 0 or n_img == 0 else
+                         f"gtsfm_global_ba_calib: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
+    rc = L.gtsfm_global_ba_calib(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T,
+                                 _ptr(n_tracks_dev), n_meas, _ptr(point), _ptr(track_valid), _ptr(meas_valid),
+                                 _ptr(wRc), _ptr(wtc), _ptr(calib), _ptr(cam_valid), n_img, _flag(robust),
+                                 float(measurement_sigma), float(cam_pose3_prior_sigma), _flag(shared_calib),
+                                 float(calibration_prior_sigma), int(max_iterations), float(pcg_rel_tol),
+                                 int(pcg_max_iter), float(reproj_error_thresh), _ptr(ws),
+                                 ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(wRc_out),
+                                 _ptr(wtc_out), _ptr(calib_out), _ptr(point_out), _ptr(track_keep), _ptr(cam_keep),
+                                 _ptr(stats), native.stream_handle(stream))
+    native.check(rc, "gtsfm_global_ba_calib")
+    return GlobalBaCalibResult(wRc_out, wtc_out, point_out, track_keep, cam_keep, stats, calib_out)
+
+
+@dataclass(eq=False)
 class BaInputResult:
     """Outputs of assemble_ba_input, all on the device: cam_keep (n_img,) and track_keep (T,) uint8, track_len (T,)
     int32, stats (6,) int64 in the order of native.BA_INPUT_STATS_FIELDS."""

@@ -94,7 +94,9 @@ class MultiViewOptimizer:
           6. triangulation (DataAssociation.run_triangulation_arrays);
           7. DataAssociation.assemble_arrays;
           8. run_ba_arrays with cam_valid = cam_keep, the track-valid byte = track_keep and the BA module's last
-             reprojection threshold, as run_ba does.
+             reprojection threshold, as run_ba does. The BA module is used as it was given: one built with
+             refine_calibration=True refines the calibration, and its BaArrays.calib is part of the result (`run`
+             builds the optimised and filtered cameras from it); the dense stage does not read it yet.
 
         Host synchronisations are those of the stages and no other: the track counts that size the track arrays
         (DsfTracksEstimator.run_arrays); translation averaging's `counts` and its recovery's control scalars; the
@@ -197,11 +199,15 @@ class MultiViewOptimizer:
         t_off, t_img, t_kp = (a.cpu().numpy() for a in (r.tracks.offsets, r.tracks.image, r.tracks.keypoint))
         inlier = r.triangulated.inlier.cpu().numpy()
 
-        def data(wRc, wtc, point, cam_mask, track_mask) -> BaData:
+        def data(wRc, wtc, point, cam_mask, track_mask, calib=None) -> BaData:
+            """calib: the (n_img, 5) calibration a BA module with refine_calibration=True returns, or None."""
             wRc, wtc, point = wRc.cpu().numpy(), wtc.cpu().numpy(), point.cpu().numpy()
-            cams = {int(i): geometry.PinholeCameraCal3Bundler(geometry.Pose3(geometry.Rot3(wRc[i]), wtc[i]),
-                                                              all_intrinsics[i])
+            calib = None if calib is None else calib.cpu().numpy()
+            cams = {int(i): geometry.PinholeCameraCal3Bundler(
+                        geometry.Pose3(geometry.Rot3(wRc[i]), wtc[i]),
+                        all_intrinsics[i] if calib is None else geometry.Cal3Bundler(*(float(v) for v in calib[i])))
                     for i in np.flatnonzero(cam_mask.cpu().numpy())}
+            cals = None if calib is None else {i: calib[i].copy() for i in cams}
             tracks = []
             for t in np.flatnonzero(track_mask.cpu().numpy()):
                 track = SfmTrack(point[t])
@@ -210,7 +216,7 @@ class MultiViewOptimizer:
                         track.addMeasurement(int(t_img[m]),
                                              np.asarray(coords[t_img[m]][t_kp[m]], np.float64).reshape(2))
                 tracks.append(track)
-            return BaData(cams, tracks)
+            return BaData(cams, tracks, cals)
 
         cam0 = r.cameras
         ba_input = data(cam0[0], cam0[1], r.triangulated.point, r.ba_input.cam_keep, r.ba_input.track_keep)
@@ -218,6 +224,6 @@ class MultiViewOptimizer:
             return empty
         if int(r.ba.stats[9].item()) == native.GBA_STATUS_NOTHING:  # bundle_adjustment.py:319-324
             return ba_input, ba_input, ba_input
-        ba_output = data(r.ba.wRc, r.ba.wtc, r.ba.point, r.ba_input.cam_keep, r.ba_input.track_keep)
-        ba_filtered = data(r.ba.wRc, r.ba.wtc, r.ba.point, r.ba.cam_keep, r.ba.track_keep)
+        ba_output = data(r.ba.wRc, r.ba.wtc, r.ba.point, r.ba_input.cam_keep, r.ba_input.track_keep, r.ba.calib)
+        ba_filtered = data(r.ba.wRc, r.ba.wtc, r.ba.point, r.ba.cam_keep, r.ba.track_keep, r.ba.calib)
         return ba_input, ba_output, ba_filtered

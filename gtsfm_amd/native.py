@@ -60,6 +60,8 @@ GBA_STATUS_OK = 0
 GBA_STATUS_NOTHING = 1  # no participating track or no modelled camera: the reference's early return
 GBA_STATS_FIELDS = ("initial_error", "final_error", "lm_iterations", "lm_trials", "pcg_iterations", "pcg_cap_hits",
                     "cameras_modelled", "tracks_participating", "tracks_kept", "status")
+# gtsfm_global_ba_calib's d_stats: the ten above, then the calibration variables and the largest |f_out - f_in| / f_in
+GBA_CALIB_STATS_FIELDS = GBA_STATS_FIELDS + ("calibration_variables", "max_rel_focal_change")
 TA_STATUS_OK = 0
 TA_STATUS_NOTHING = 1  # no measurement kept
 TA_STATUS_NOT_FINITE = 2
@@ -197,6 +199,13 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_double, c_int, c_double, c_void_p,
          c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_global_ba_calib_workspace_bytes": (c_size_t, [c_longlong, c_longlong, c_int]),
+    "gtsfm_global_ba_calib": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_int, c_double, c_int, c_double, c_int,
+         c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "gtsfm_transavg_measurements_workspace_bytes": (c_size_t, [c_int, c_longlong, c_longlong, c_int]),
     "gtsfm_transavg_measurements": (

@@ -532,8 +532,10 @@ int gtsfm_triangulate_tracks(const int* d_track_offsets, const int* d_track_img,
  * camera, one point per participating track. Factors: a reprojection factor per usable measurement of a participating
  * track; PriorFactorPose3 on the modelled camera of lowest index at its initial pose, isotropic
  * cam_pose3_prior_sigma; PriorFactorPoint3, sigma 0.1, on the first participating track at its initial point.
- * Calibration is held fixed at k1 = k2 = 0, the approximation gtsfm_ba2_batched states (the limit of the reference's
- * 1e-5 calibration prior), so shared_calib has no effect. BetweenFactorPose3 relative-pose priors are not built.
+ * This entry point holds calibration fixed at k1 = k2 = 0, the approximation gtsfm_ba2_batched states (the limit of the
+ * reference's 1e-5 calibration prior as that sigma goes to 0), so the reference's shared_calib does not enter it;
+ * gtsfm_global_ba_calib below is the same solver with the Cal3Bundler calibration refined, per camera or shared.
+ * BetweenFactorPose3 relative-pose priors are not built.
  * Taken from gtsfm_ba2_batched (ba2.hip), generalised from camera 0 = identity to an arbitrary first camera: the
  * reprojection residual and its Jacobians (pose in the body frame, rotation first), the Huber loss and sqrt-weight
  * scaling of the rows, a measurement with z <= 0 contributing nothing to the linear system or the cost, the pose prior
@@ -577,6 +579,54 @@ int gtsfm_global_ba(const int* d_track_offsets, const int* d_track_img, const vo
                     int pcg_max_iter, double reproj_error_thresh, void* d_workspace, size_t workspace_bytes,
                     double* d_wRc_out, double* d_wtc_out, double* d_point_out, uint8_t* d_track_keep,
                     uint8_t* d_cam_keep, double* d_stats, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Global bundle adjustment with the calibration refined: gtsfm/bundle/bundle_adjustment.py:58-66 ("refines global pose
+ * estimates and intrinsics of cameras"), :103-131 and :180-208 (a K(i) variable per camera, or a single K(0) when
+ * shared_calib = True, in every GeneralSFMFactor2Cal3Bundler, and a PriorFactorCal3Bundler of
+ * calibration_prior_noise_sigma on each calibration variable), :188-195 and :258-260 (the shared variable).
+ *
+ * Everything gtsfm_global_ba's block states holds here, with these differences.
+ * Cameras: d_calib[n_img][5] = (f, k1, k2, u0, v0), the argument order of GTSAM 4.2's Cal3Bundler, replaces
+ * d_intrinsics. Projection of a camera-frame point pc: x = pc_x / pc_z, y = pc_y / pc_z, r2 = x^2 + y^2,
+ * g = 1 + (k1 + k2 r2) r2, u = f g x + u0, v = f g y + v0. d uv / d (x, y) = f (g I + 2 (k1 + 2 k2 r2) [x; y][x y]),
+ * chained with the pinhole Jacobians of pose (body frame, rotation first) and point; d uv / d (f, k1, k2) =
+ * [[x g, f x r2, f x r2^2], [y g, f y r2, f y r2^2]]. u0 and v0 are not variables (Cal3Bundler::dim() == 3).
+ * Calibration variables: with shared_calib = 0 one (f, k1, k2) per modelled camera, with its prior at that camera's
+ * input calibration; with shared_calib = 1 a single one, initialised from and with its prior at the calibration of the
+ * modelled camera of lowest index, whose u0, v0 are then used for EVERY camera. The prior's residual is
+ * (f, k1, k2) - (f, k1, k2)_initial, isotropic calibration_prior_sigma (the reference's default is 1e-5, at which this
+ * call returns gtsfm_global_ba's result to rounding on undistorted input); the retraction is (f, k1, k2) + delta.
+ * The reduced system has 9 x 9 blocks (pose + calibration) per camera, or, shared, 6 x 6 blocks per camera and one
+ * 3 x 3 border block coupled to every camera; the unknown vector is [C][9] or [6C | 3]. The preconditioner is the inverse
+ * of the diagonal blocks of the damped Schur complement, the border block included. In shared mode each camera's
+ * workgroup writes its share of the border (of its diagonal block and right-hand side, and of the border row of every
+ * product q = S p) to a slot of its own, and one workgroup sums the slots in a fixed order. No floating-point atomics:
+ * two calls return byte-identical outputs. The filter reprojects with the refined, distorted model.
+ *
+ * Outputs: gtsfm_global_ba's, plus d_calib_out[n_img][5]: a modelled camera's refined calibration (shared mode: the
+ * shared one, the same five values in every modelled camera's row); a camera that is not modelled is copied through
+ * bit for bit. d_stats[12]: gtsfm_global_ba's ten slots, then the number of calibration variables and the largest
+ * |f_out - f_in| / f_in of a modelled camera. Status codes, argument checks and capacity errors are gtsfm_global_ba's;
+ * in addition calibration_prior_sigma not > 0 or shared_calib outside {0, 1} returns GTSFM_ERR_ARG. On status 1 d_calib
+ * is copied through and the two new slots are 0.
+ * Workspace: 208 bytes per measurement for the linearisation (Jx 2 x 6, Jk 2 x 3, Jp 2 x 3, b 2) plus 8 for the two
+ * indices, about 350 bytes per track (as gtsfm_global_ba) and about 2.2 KiB per camera (two 9 x 9 blocks, the poses and
+ * calibrations twice, the border slots and six vectors of 9 entries). As gtsfm_global_ba the call SYNCHRONISES its
+ * stream and allocates nothing.
+ * ---------------------------------------------------------------------------------------------- */
+/* 0 for an empty shape (a size <= 0) or an unsupported one (n_tracks or n_meas >= 2^31 - 1, n_img > 2^20). */
+size_t gtsfm_global_ba_calib_workspace_bytes(long long n_tracks, long long n_meas, int n_img);
+
+int gtsfm_global_ba_calib(const int* d_track_offsets, const int* d_track_img, const void* d_track_uv, int uv_is_f64,
+                          long long n_tracks, const long long* d_n_tracks, long long n_meas, const double* d_point,
+                          const uint8_t* d_track_valid, const uint8_t* d_meas_valid, const double* d_wRc,
+                          const double* d_wtc, const double* d_calib, const uint8_t* d_cam_valid, int n_img,
+                          int robust, double measurement_sigma, double cam_pose3_prior_sigma, int shared_calib,
+                          double calibration_prior_sigma, int max_iterations, double pcg_rel_tol, int pcg_max_iter,
+                          double reproj_error_thresh, void* d_workspace, size_t workspace_bytes, double* d_wRc_out,
+                          double* d_wtc_out, double* d_calib_out, double* d_point_out, uint8_t* d_track_keep,
+                          uint8_t* d_cam_keep, double* d_stats, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Translation averaging, 1DSfM: gtsfm/averaging/translation/averaging_1dsfm.py TranslationAveraging1DSFM, in three

@@ -13,7 +13,13 @@ product kernels' rate, since the vector step and the read-back are inside it. Tw
 --restatement the numpy restatement (tests/global_ba_ref.py) and the kernel both run a --sample-images camera scene of
 the same generator and must agree.
 
+--refine-calibration {per-camera,shared} also times gtsfm_global_ba_calib (calibration refined, prior sigma
+--calibration-sigma) on the same input in the same run, f stored as (f, 0, 0, u0, v0), and reports its call time, its
+time per PCG iteration and both as a ratio to the fixed-calibration call; with --restatement it is checked against
+tests/global_ba_calib_ref.py on the sample scene seen by a distorted camera.
+
     python tools/global_ba_bench.py [--images 1000] --restatement [--out bench_out/global_ba.jsonl]
+    python tools/global_ba_bench.py --refine-calibration per-camera --restatement
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import global_ba_calib_ref as cref  # noqa: E402
 import global_ba_ref as ref  # noqa: E402
 from gtsfm_amd import device, native  # noqa: E402
 
@@ -46,12 +53,69 @@ def to_dev(s, dev):
             t(s["cam_valid"], np.uint8))
 
 
-def timed(args, **kw):
+def timed(args, fn=None, **kw):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    r = device.global_ba(*args, **kw)
+    r = (fn or device.global_ba)(*args, **kw)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, r
+
+
+def refine_calibration_bench(a, s, args, dev, fixed):
+    """gtsfm_global_ba_calib on the input the fixed-calibration call was just timed on: call time, time per PCG
+    iteration by the same difference of two caps, both against `fixed`; with --restatement the sample-scene check."""
+    shared = a.refine_calibration == "shared"
+    K = s["intr"]
+    calib = torch.from_numpy(np.concatenate([K[:, :1], np.zeros((len(K), 2)), K[:, 1:]], 1)).to(dev)
+    cargs = args[:8] + (calib,) + args[9:]
+    n_meas = len(s["img"])
+    ws = torch.empty(native.lib().gtsfm_global_ba_calib_workspace_bytes(a.tracks, n_meas, a.images),
+                     dtype=torch.uint8, device=dev)
+    kw = dict(robust=True, reproj_error_thresh=3.0, workspace=ws, shared_calib=shared,
+              calibration_prior_sigma=a.calibration_sigma, fn=device.global_ba_calib)
+    _, warm = timed(cargs, max_iterations=a.max_iterations, **kw)
+    times, last = [], None
+    for _ in range(a.repeats):
+        ms, last = timed(cargs, max_iterations=a.max_iterations, **kw)
+        times.append(ms)
+    for k in ("wRc", "wtc", "point", "track_keep", "cam_keep", "stats", "calib"):
+        assert getattr(warm, k).cpu().numpy().tobytes() == getattr(last, k).cpu().numpy().tobytes(), k
+    st = last.stats.cpu().numpy()
+    diff = []
+    for _ in range(a.repeats):
+        ta, ra = timed(cargs, max_iterations=1, pcg_max_iter=a.cap_a, **kw)
+        tb, rb = timed(cargs, max_iterations=1, pcg_max_iter=a.cap_b, **kw)
+        sa, sb = ra.stats.cpu().numpy(), rb.stats.cpu().numpy()
+        if sa[3] == sb[3] and sb[4] > sa[4]:
+            diff.append((tb - ta) / (sb[4] - sa[4]))
+    per_iter = statistics.median(diff) if diff else float("nan")
+    out = {"refine_calibration": a.refine_calibration, "calibration_sigma": a.calibration_sigma,
+           "calib_call_ms_median": statistics.median(times), "calib_call_ms_min": min(times),
+           "calib_lm_iterations": st[2], "calib_lm_trials": st[3], "calib_pcg_iterations": st[4],
+           "calib_ms_per_lm_trial": statistics.median(times) / max(st[3], 1), "calib_ms_per_pcg_iteration": per_iter,
+           "calib_final_error": st[1], "calib_variables": st[10], "calib_max_rel_focal_change": st[11],
+           "calib_byte_identical": True,
+           "calib_over_fixed_call": statistics.median(times) / fixed["call_ms_median"],
+           "calib_over_fixed_lm_trial": (statistics.median(times) / max(st[3], 1)) / fixed["ms_per_lm_trial"],
+           "calib_over_fixed_pcg_iteration": per_iter / fixed["ms_per_pcg_iteration"]}
+    if a.restatement:
+        s2 = cref.distort_scene(ref.ring_scene(a.sample_images, 15 * a.sample_images, 4, 9, a.seed + 1))
+        s2["uv"] = s2["uv"].astype(np.float32).astype(np.float64)
+        opts = dict(robust=True, max_iterations=a.max_iterations, reproj_error_thresh=3.0, shared_calib=shared,
+                    calibration_prior_sigma=a.calibration_sigma)
+        want = cref.global_ba_calib_ref(*cref.call_args(s2), **opts)
+        d2 = to_dev(s2, dev)
+        got = device.global_ba_calib(*d2[:8], torch.from_numpy(s2["calib"]).to(dev), *d2[9:], **opts)
+        gs = got.stats.cpu().numpy()
+        cams = np.arange(a.sample_images)
+        rot, tr = ref.pose_diff(got.wRc.cpu().numpy(), got.wtc.cpu().numpy(), want.wRc, want.wtc, cams)
+        df, dk = cref.calib_diff(got.calib.cpu().numpy(), want.calib, cams)
+        out.update(calib_sample_rot_deg=rot, calib_sample_trans_rel=tr, calib_sample_f_rel=df, calib_sample_k_abs=dk,
+                   calib_sample_lm_counts_equal=bool((gs[2:4] == want.stats[2:4]).all()),
+                   calib_sample_keep_equal=bool(np.array_equal(got.track_keep.cpu().numpy(), want.track_keep)),
+                   calib_sample_ref_margin=want.min_margin)
+        assert rot <= 1e-4 and tr <= 1e-6 and df <= 1e-6 and dk <= 1e-6, (rot, tr, df, dk)
+    return out
 
 
 def main() -> None:
@@ -65,6 +129,8 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--restatement", action="store_true")
     ap.add_argument("--sample-images", type=int, default=40)
+    ap.add_argument("--refine-calibration", choices=("off", "per-camera", "shared"), default="off")
+    ap.add_argument("--calibration-sigma", type=float, default=50.0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     native.require_gpu()
@@ -104,6 +170,8 @@ def main() -> None:
         "product_bytes_per_s_lower_bound": product_bytes / (per_iter_ms * 1e-3) if diff else None,
         "initial_error": st[0], "final_error": st[1], "tracks_kept": st[8], "byte_identical": True,
     }
+    if a.refine_calibration != "off":
+        res.update(refine_calibration_bench(a, s, args, dev, res))
     if a.restatement:
         s2 = ref.ring_scene(a.sample_images, 15 * a.sample_images, 4, 9, a.seed + 1)
         t0 = time.perf_counter()
