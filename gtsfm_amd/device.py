@@ -804,6 +804,32 @@ class GlobalBaResult:
     stats: torch.Tensor
 
 
+def _global_ba_prepare(fn: str, n_stats: int, track_offsets, track_img, track_uv, n_tracks, n_tracks_dev, point,
+                       check_cameras, track_valid, meas_valid, stream, workspace):
+    """What global_ba and global_ba_calib do before their native call `fn`: the argument checks (check_cameras() checks
+    the caller's camera arrays and returns n_img), the outputs they share and the workspace. Returns T, n_meas,
+    uv_is_f64, n_img, track_valid as uint8, (wRc_out, wtc_out, point_out, track_keep, cam_keep, stats) and the
+    workspace."""
+    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
+    _check(point, "point", _F64, min_numel=3 * T)
+    n_img = check_cameras()
+    if track_valid is not None and track_valid.dtype == torch.bool:
+        track_valid = track_valid.to(torch.uint8)
+    _check(track_valid, "track_valid", _U8, min_numel=T, optional=True)
+    _check(meas_valid, "meas_valid", _U8, numel=n_meas, optional=True)
+    dev = track_offsets.device
+    outs = (torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev),
+            torch.empty((n_img, 3), dtype=torch.float64, device=dev),
+            torch.empty((T, 3), dtype=torch.float64, device=dev),
+            torch.empty(T, dtype=torch.uint8, device=dev),
+            torch.empty(n_img, dtype=torch.uint8, device=dev),
+            torch.empty(n_stats, dtype=torch.float64, device=dev))
+    ws = _take_workspace(getattr(native.lib(), fn + "_workspace_bytes")(T, n_meas, n_img), dev, workspace, stream,
+                         None if T == 0 or n_meas == 0 or n_img == 0 else
+                         f"{fn}: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
+    return T, n_meas, uv_is_f64, n_img, track_valid, outs, ws
+
+
 def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: torch.Tensor, point: torch.Tensor,
               track_valid: Optional[torch.Tensor], meas_valid: Optional[torch.Tensor], wRc: torch.Tensor,
               wtc: torch.Tensor, intrinsics: torch.Tensor, cam_valid: Optional[torch.Tensor], robust: bool = False,
@@ -818,34 +844,18 @@ def global_ba(track_offsets: torch.Tensor, track_img: torch.Tensor, track_uv: to
     (T,) uint8 or bool or None, meas_valid (n_meas,) uint8 or None (the triangulation's inlier bytes). The call runs
     its LM / PCG control flow on the host and synchronises the stream; only those control scalars reach the host.
     workspace_bytes below the query's value is passed as is (tests of the capacity error)."""
-    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
-    _check(point, "point", _F64, min_numel=3 * T)
-    n_img = _check_cameras(wRc, wtc, intrinsics, cam_valid)
-    if track_valid is not None and track_valid.dtype == torch.bool:
-        track_valid = track_valid.to(torch.uint8)
-    _check(track_valid, "track_valid", _U8, min_numel=T, optional=True)
-    _check(meas_valid, "meas_valid", _U8, numel=n_meas, optional=True)
-    dev = track_offsets.device
-    wRc_out = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
-    wtc_out = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
-    point_out = torch.empty((T, 3), dtype=torch.float64, device=dev)
-    track_keep = torch.empty(T, dtype=torch.uint8, device=dev)
-    cam_keep = torch.empty(n_img, dtype=torch.uint8, device=dev)
-    stats = torch.empty(10, dtype=torch.float64, device=dev)
-    L = native.lib()
-    ws = _take_workspace(L.gtsfm_global_ba_workspace_bytes(T, n_meas, n_img), dev, workspace, stream,
-                         None if T == 0 or n_meas == 0 or n_img == 0 else
-                         f"gtsfm_global_ba: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
-    rc = L.gtsfm_global_ba(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T, _ptr(n_tracks_dev),
-                           n_meas, _ptr(point), _ptr(track_valid), _ptr(meas_valid), _ptr(wRc), _ptr(wtc),
-                           _ptr(intrinsics), _ptr(cam_valid), n_img, _flag(robust), float(measurement_sigma),
-                           float(cam_pose3_prior_sigma), int(max_iterations), float(pcg_rel_tol), int(pcg_max_iter),
-                           float(reproj_error_thresh), _ptr(ws),
-                           ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(wRc_out),
-                           _ptr(wtc_out), _ptr(point_out), _ptr(track_keep), _ptr(cam_keep), _ptr(stats),
-                           native.stream_handle(stream))
+    T, n_meas, uv_is_f64, n_img, track_valid, outs, ws = _global_ba_prepare(
+        "gtsfm_global_ba", 10, track_offsets, track_img, track_uv, n_tracks, n_tracks_dev, point,
+        lambda: _check_cameras(wRc, wtc, intrinsics, cam_valid), track_valid, meas_valid, stream, workspace)
+    rc = native.lib().gtsfm_global_ba(
+        _ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T, _ptr(n_tracks_dev), n_meas, _ptr(point),
+        _ptr(track_valid), _ptr(meas_valid), _ptr(wRc), _ptr(wtc), _ptr(intrinsics), _ptr(cam_valid), n_img,
+        _flag(robust), float(measurement_sigma), float(cam_pose3_prior_sigma), int(max_iterations),
+        float(pcg_rel_tol), int(pcg_max_iter), float(reproj_error_thresh), _ptr(ws),
+        ws.numel() if workspace_bytes is None else int(workspace_bytes), *map(_ptr, outs),
+        native.stream_handle(stream))
     native.check(rc, "gtsfm_global_ba")
-    return GlobalBaResult(wRc_out, wtc_out, point_out, track_keep, cam_keep, stats)
+    return GlobalBaResult(*outs)
 
 
 @dataclass(eq=False)
@@ -870,40 +880,29 @@ def global_ba_calib(track_offsets: torch.Tensor, track_img: torch.Tensor, track_
 
     The arguments are global_ba's, with calib (n_img, 5) float64 = (f, k1, k2, u0, v0) in place of intrinsics, and the
     prior sigma of the calibration variables. Like global_ba the call synchronises the stream."""
-    T, n_meas, uv_is_f64 = _track_csr(track_offsets, track_img, track_uv, n_tracks, n_tracks_dev)
-    _check(point, "point", _F64, min_numel=3 * T)
-    n_img = calib.numel() // 5
-    _check(wRc, "wRc", _F64, numel=9 * n_img)
-    _check(wtc, "wtc", _F64, numel=3 * n_img)
-    _check(calib, "calib", _F64, numel=5 * n_img)
-    _check(cam_valid, "cam_valid", _U8, numel=n_img, optional=True)
-    if track_valid is not None and track_valid.dtype == torch.bool:
-        track_valid = track_valid.to(torch.uint8)
-    _check(track_valid, "track_valid", _U8, min_numel=T, optional=True)
-    _check(meas_valid, "meas_valid", _U8, numel=n_meas, optional=True)
-    dev = track_offsets.device
-    wRc_out = torch.empty((n_img, 3, 3), dtype=torch.float64, device=dev)
-    wtc_out = torch.empty((n_img, 3), dtype=torch.float64, device=dev)
-    calib_out = torch.empty((n_img, 5), dtype=torch.float64, device=dev)
-    point_out = torch.empty((T, 3), dtype=torch.float64, device=dev)
-    track_keep = torch.empty(T, dtype=torch.uint8, device=dev)
-    cam_keep = torch.empty(n_img, dtype=torch.uint8, device=dev)
-    stats = torch.empty(12, dtype=torch.float64, device=dev)
-    L = native.lib()
-    ws = _take_workspace(L.gtsfm_global_ba_calib_workspace_bytes(T, n_meas, n_img), dev, workspace, stream,
-                         None if T == 0 or n_meas == 0 or n_img == 0 else
-                         f"gtsfm_global_ba_calib: unsupported shape {T} tracks, {n_meas} measurements, {n_img} images")
-    rc = L.gtsfm_global_ba_calib(_ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T,
-                                 _ptr(n_tracks_dev), n_meas, _ptr(point), _ptr(track_valid), _ptr(meas_valid),
-                                 _ptr(wRc), _ptr(wtc), _ptr(calib), _ptr(cam_valid), n_img, _flag(robust),
-                                 float(measurement_sigma), float(cam_pose3_prior_sigma), _flag(shared_calib),
-                                 float(calibration_prior_sigma), int(max_iterations), float(pcg_rel_tol),
-                                 int(pcg_max_iter), float(reproj_error_thresh), _ptr(ws),
-                                 ws.numel() if workspace_bytes is None else int(workspace_bytes), _ptr(wRc_out),
-                                 _ptr(wtc_out), _ptr(calib_out), _ptr(point_out), _ptr(track_keep), _ptr(cam_keep),
-                                 _ptr(stats), native.stream_handle(stream))
+    def check_cameras() -> int:
+        n_img = calib.numel() // 5
+        _check(wRc, "wRc", _F64, numel=9 * n_img)
+        _check(wtc, "wtc", _F64, numel=3 * n_img)
+        _check(calib, "calib", _F64, numel=5 * n_img)
+        _check(cam_valid, "cam_valid", _U8, numel=n_img, optional=True)
+        return n_img
+
+    T, n_meas, uv_is_f64, n_img, track_valid, outs, ws = _global_ba_prepare(
+        "gtsfm_global_ba_calib", 12, track_offsets, track_img, track_uv, n_tracks, n_tracks_dev, point,
+        check_cameras, track_valid, meas_valid, stream, workspace)
+    wRc_out, wtc_out, point_out, track_keep, cam_keep, stats = outs
+    calib_out = torch.empty((n_img, 5), dtype=torch.float64, device=track_offsets.device)
+    rc = native.lib().gtsfm_global_ba_calib(
+        _ptr(track_offsets), _ptr(track_img), _ptr(track_uv), uv_is_f64, T, _ptr(n_tracks_dev), n_meas, _ptr(point),
+        _ptr(track_valid), _ptr(meas_valid), _ptr(wRc), _ptr(wtc), _ptr(calib), _ptr(cam_valid), n_img,
+        _flag(robust), float(measurement_sigma), float(cam_pose3_prior_sigma), _flag(shared_calib),
+        float(calibration_prior_sigma), int(max_iterations), float(pcg_rel_tol), int(pcg_max_iter),
+        float(reproj_error_thresh), _ptr(ws), ws.numel() if workspace_bytes is None else int(workspace_bytes),
+        _ptr(wRc_out), _ptr(wtc_out), _ptr(calib_out), _ptr(point_out), _ptr(track_keep), _ptr(cam_keep),
+        _ptr(stats), native.stream_handle(stream))
     native.check(rc, "gtsfm_global_ba_calib")
-    return GlobalBaCalibResult(wRc_out, wtc_out, point_out, track_keep, cam_keep, stats, calib_out)
+    return GlobalBaCalibResult(*outs, calib_out)
 
 
 @dataclass(eq=False)

@@ -42,6 +42,7 @@ from gtsfm_amd import device, native  # noqa: E402
 # gba.hip per factor measurement and product: pass 1 reads Jx, Jp (144 B of the 160 B record), the camera's p (48 B), the
 # image index (4 B); pass 2 reads Jx, Jp (144 B), the track's y (24 B), the camera-major index and the track index (8 B)
 PRODUCT_BYTES_PER_MEASUREMENT = 144 + 48 + 4 + 144 + 24 + 8
+FIELDS = ("wRc", "wtc", "point", "track_keep", "cam_keep", "stats")  # of a result, compared byte for byte
 
 
 def to_dev(s, dev):
@@ -53,12 +54,34 @@ def to_dev(s, dev):
             t(s["cam_valid"], np.uint8))
 
 
-def timed(args, fn=None, **kw):
+def timed(args, fn, **kw):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    r = (fn or device.global_ba)(*args, **kw)
+    r = fn(*args, **kw)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, r
+
+
+def time_solver(a, fn, args, fields, **kw):
+    """What both solvers are measured by: a warm-up call, --repeats timed calls, the byte-identity of `fields` between
+    the warm-up and the last call, and the PCG iteration by difference (one LM iteration whose solves are capped at
+    --cap-a and --cap-b; both caps must bind for the difference to be exact). Returns the call times, the last call's
+    stats and the ms per PCG iteration (nan when no pair of calls was comparable)."""
+    _, warm = timed(args, fn, max_iterations=a.max_iterations, **kw)
+    times, last = [], None
+    for _ in range(a.repeats):
+        ms, last = timed(args, fn, max_iterations=a.max_iterations, **kw)
+        times.append(ms)
+    for k in fields:
+        assert getattr(warm, k).cpu().numpy().tobytes() == getattr(last, k).cpu().numpy().tobytes(), k
+    diff = []
+    for _ in range(a.repeats):
+        ta, ra = timed(args, fn, max_iterations=1, pcg_max_iter=a.cap_a, **kw)
+        tb, rb = timed(args, fn, max_iterations=1, pcg_max_iter=a.cap_b, **kw)
+        sa, sb = ra.stats.cpu().numpy(), rb.stats.cpu().numpy()
+        if sa[3] == sb[3] and sb[4] > sa[4]:
+            diff.append((tb - ta) / (sb[4] - sa[4]))
+    return times, last.stats.cpu().numpy(), statistics.median(diff) if diff else float("nan")
 
 
 def refine_calibration_bench(a, s, args, dev, fixed):
@@ -71,24 +94,9 @@ def refine_calibration_bench(a, s, args, dev, fixed):
     n_meas = len(s["img"])
     ws = torch.empty(native.lib().gtsfm_global_ba_calib_workspace_bytes(a.tracks, n_meas, a.images),
                      dtype=torch.uint8, device=dev)
-    kw = dict(robust=True, reproj_error_thresh=3.0, workspace=ws, shared_calib=shared,
-              calibration_prior_sigma=a.calibration_sigma, fn=device.global_ba_calib)
-    _, warm = timed(cargs, max_iterations=a.max_iterations, **kw)
-    times, last = [], None
-    for _ in range(a.repeats):
-        ms, last = timed(cargs, max_iterations=a.max_iterations, **kw)
-        times.append(ms)
-    for k in ("wRc", "wtc", "point", "track_keep", "cam_keep", "stats", "calib"):
-        assert getattr(warm, k).cpu().numpy().tobytes() == getattr(last, k).cpu().numpy().tobytes(), k
-    st = last.stats.cpu().numpy()
-    diff = []
-    for _ in range(a.repeats):
-        ta, ra = timed(cargs, max_iterations=1, pcg_max_iter=a.cap_a, **kw)
-        tb, rb = timed(cargs, max_iterations=1, pcg_max_iter=a.cap_b, **kw)
-        sa, sb = ra.stats.cpu().numpy(), rb.stats.cpu().numpy()
-        if sa[3] == sb[3] and sb[4] > sa[4]:
-            diff.append((tb - ta) / (sb[4] - sa[4]))
-    per_iter = statistics.median(diff) if diff else float("nan")
+    times, st, per_iter = time_solver(a, device.global_ba_calib, cargs, FIELDS + ("calib",), robust=True,
+                                      reproj_error_thresh=3.0, workspace=ws, shared_calib=shared,
+                                      calibration_prior_sigma=a.calibration_sigma)
     out = {"refine_calibration": a.refine_calibration, "calibration_sigma": a.calibration_sigma,
            "calib_call_ms_median": statistics.median(times), "calib_call_ms_min": min(times),
            "calib_lm_iterations": st[2], "calib_lm_trials": st[3], "calib_pcg_iterations": st[4],
@@ -140,25 +148,9 @@ def main() -> None:
     n_meas = len(s["img"])
     ws = torch.empty(native.lib().gtsfm_global_ba_workspace_bytes(a.tracks, n_meas, a.images), dtype=torch.uint8,
                      device=dev)
-    kw = dict(robust=True, reproj_error_thresh=3.0, workspace=ws)
-    _, warm = timed(args, max_iterations=a.max_iterations, **kw)
-    times, last = [], None
-    for _ in range(a.repeats):
-        ms, last = timed(args, max_iterations=a.max_iterations, **kw)
-        times.append(ms)
-    for k in ("wRc", "wtc", "point", "track_keep", "cam_keep", "stats"):
-        assert getattr(warm, k).cpu().numpy().tobytes() == getattr(last, k).cpu().numpy().tobytes(), k
-    st = last.stats.cpu().numpy()
+    times, st, per_iter_ms = time_solver(a, device.global_ba, args, FIELDS, robust=True, reproj_error_thresh=3.0,
+                                         workspace=ws)
     factors = n_meas  # every measurement is a factor in this scene
-    # the PCG iteration by difference (one LM iteration; both caps must bind for the difference to be exact)
-    diff = []
-    for _ in range(a.repeats):
-        ta, ra = timed(args, max_iterations=1, pcg_max_iter=a.cap_a, **kw)
-        tb, rb = timed(args, max_iterations=1, pcg_max_iter=a.cap_b, **kw)
-        sa, sb = ra.stats.cpu().numpy(), rb.stats.cpu().numpy()
-        if sa[3] == sb[3] and sb[4] > sa[4]:
-            diff.append((tb - ta) / (sb[4] - sa[4]))
-    per_iter_ms = statistics.median(diff) if diff else float("nan")
     product_bytes = PRODUCT_BYTES_PER_MEASUREMENT * factors
     res = {
         "tool": "global_ba_bench", "images": a.images, "tracks": a.tracks, "measurements": n_meas,
@@ -167,7 +159,7 @@ def main() -> None:
         "pcg_cap_hits": st[5], "pcg_iterations_per_solve": st[4] / max(st[3], 1),
         "ms_per_lm_trial": statistics.median(times) / max(st[3], 1), "ms_per_pcg_iteration": per_iter_ms,
         "product_algorithmic_bytes": product_bytes,
-        "product_bytes_per_s_lower_bound": product_bytes / (per_iter_ms * 1e-3) if diff else None,
+        "product_bytes_per_s_lower_bound": None if np.isnan(per_iter_ms) else product_bytes / (per_iter_ms * 1e-3),
         "initial_error": st[0], "final_error": st[1], "tracks_kept": st[8], "byte_identical": True,
     }
     if a.refine_calibration != "off":
