@@ -49,10 +49,15 @@ __host__ __device__ constexpr int conv3_nt(int ks) { return ks == 3 ? 2 : 1; }
 __host__ __device__ constexpr int conv3_rows(int ks) { return 2 * conv3_rp(ks); }
 __host__ __device__ constexpr int conv3_threads(int ks) { return 64 * (4 / conv3_nt(ks)) * conv3_rp(ks); }
 
-template <int KS, bool POOL>
+// DIL: the taps' spacing (torch's dilation, with padding DIL * (KS / 2) so the output keeps the input's size): the
+// staged patch grows its halo to DIL * (KS / 2) pixels and tap (ky, kx) reads patch pixel (row + DIL ky, col + DIL kx);
+// everything else, the weight layout included, is the undilated kernel's. DIL = 2 is D2-Net's conv4 (d2net.hip); at
+// DIL = 1 every constant below is what it was, so the other callers' code is unchanged.
+template <int KS, bool POOL, int DIL = 1>
 __global__ __launch_bounds__(conv3_threads(KS), 1) void conv3_kernel(ConvArgs a, const __bf16* __restrict__ w3) {
     constexpr int kConv3NT = conv3_nt(KS), kConv3Rows = conv3_rows(KS), kConv3Threads = conv3_threads(KS);
-    constexpr int R = KS / 2;
+    constexpr int R = DIL * (KS / 2);
+    static_assert(DIL == 1 || !POOL, "the fused max-pool epilogue is only used undilated");
     constexpr int PH = kConv3Rows + 2 * R, PW = 32 + 2 * R;
     constexpr int kPU = PH * PW * 2;             // patch staging units (pixel, 8-channel half)
     constexpr int kWU = KS * KS * 3 * 64 * 2;    // weight staging units (tap, plane, cout, half)
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(conv3_threads(KS), 1) void conv3_kernel(ConvArgs a,
         for (int ky = 0; ky < KS; ++ky)
 #pragma unroll
             for (int kx = 0; kx < KS; ++kx) {
-                const int pix = (prow + ky) * PW + pcol + kx, kk = ky * KS + kx;
+                const int pix = (prow + DIL * ky) * PW + pcol + DIL * kx, kk = ky * KS + kx;
                 const int po = swz16(pix, kh);
                 const bf16x8 a0 = *(const bf16x8*)&patch[0][pix][po];
                 const bf16x8 a1 = *(const bf16x8*)&patch[1][pix][po];

@@ -523,6 +523,75 @@ def superpoint_extract(images: torch.Tensor, weights: torch.Tensor, max_kpts: in
     return out
 
 
+@dataclass(eq=False)
+class D2NetResult:
+    """Per-image D2-Net outputs (device tensors): xy (n,k,2) float32 (x, y), scores (n,k) descending, desc (n,k,512)
+    unit-norm, count (n,), n_candidates (n,) (detections before the top-k); rows past a count are zero. dense_map
+    (n,h,w,512) only when asked for."""
+
+    xy: torch.Tensor
+    scores: torch.Tensor
+    desc: torch.Tensor
+    count: torch.Tensor
+    n_candidates: torch.Tensor
+    dense_map: Optional[torch.Tensor] = None
+
+
+def d2net_map_shape(H: int, W: int) -> Tuple[int, int]:
+    """(h, w) of D2-Net's dense map for an H x W image: two floor-halvings, then the 2x2 stride-1 average pool."""
+    return H // 2 // 2 - 1, W // 2 // 2 - 1
+
+
+def d2net_extract(images: torch.Tensor, weights: torch.Tensor, max_kpts: int, fact_i: float = 1.0,
+                  fact_j: float = 1.0, stream: Optional[torch.cuda.Stream] = None, out: Optional[D2NetResult] = None,
+                  workspace: Optional[torch.Tensor] = None, dense_map: bool = False,
+                  last_stage: Optional[int] = None) -> D2NetResult:
+    """D2-Net (single scale) on a batch of same-sized uint8 images (n, H, W, 3) RGB or (n, H, W) gray
+    (gtsfm_d2net_batched).
+
+    weights: the packed fp32 blob (gtsfm_amd.frontend.detector_descriptor.d2net.pack_d2net_weights).
+    fact_i, fact_j: row / column factors the coordinates are multiplied by (original over resized shape).
+    out: optional preallocated outputs; workspace: optional device buffer of at least gtsfm_d2net_workspace_bytes.
+    dense_map: also return the (n, h, w, 512) feature map (tests). last_stage: stop after that
+    native.GTSFM_D2NET_STAGE_* (gtsfm_d2net_stages, the benchmark's hook); None runs the whole call.
+    """
+    _check(images, "images", _U8)
+    L = native.lib()
+    _check(weights, "weights", _F32, numel=L.gtsfm_d2net_weights_floats())
+    assert images.dim() in (3, 4), f"images must be (n, H, W) or (n, H, W, 3); got {tuple(images.shape)}"
+    n, H, W = images.shape[0], images.shape[1], images.shape[2]
+    C = 1 if images.dim() == 3 else images.shape[3]
+    dev = images.device
+    if out is None:
+        out = D2NetResult(torch.zeros((n, max_kpts, 2), dtype=torch.float32, device=dev),
+                          torch.zeros((n, max_kpts), dtype=torch.float32, device=dev),
+                          torch.zeros((n, max_kpts, 512), dtype=torch.float32, device=dev),
+                          torch.zeros((n,), dtype=torch.int32, device=dev),
+                          torch.zeros((n,), dtype=torch.int32, device=dev))
+    _check(out.xy, "out.xy", _F32, shape=(n, max_kpts, 2))
+    _check(out.scores, "out.scores", _F32, shape=(n, max_kpts))
+    _check(out.desc, "out.desc", _F32, shape=(n, max_kpts, 512))
+    _check(out.count, "out.count", _I32, numel=n)
+    _check(out.n_candidates, "out.n_candidates", _I32, numel=n)
+    if n == 0:
+        return out
+    need = L.gtsfm_d2net_workspace_bytes(n, H, W, max_kpts)
+    ws = _take_workspace(need, dev, workspace, stream,
+                         unsupported=f"gtsfm_d2net_batched takes no {n} x {H} x {W} batch with max_keypoints {max_kpts}")
+    if dense_map and out.dense_map is None:
+        h, w = d2net_map_shape(H, W)
+        out.dense_map = torch.zeros((n, h, w, 512), dtype=torch.float32, device=dev)
+    args = (_ptr(images), n, H, W, C, _ptr(weights), max_kpts, float(fact_i), float(fact_j), _ptr(ws), ws.numel(),
+            _ptr(out.xy), _ptr(out.scores), _ptr(out.desc), _ptr(out.count), _ptr(out.n_candidates),
+            _ptr(out.dense_map) if dense_map else None)
+    if last_stage is None:
+        rc = L.gtsfm_d2net_batched(*args, native.stream_handle(stream))
+    else:
+        rc = L.gtsfm_d2net_stages(*args, int(last_stage), native.stream_handle(stream))
+    native.check(rc, "gtsfm_d2net_batched")
+    return out
+
+
 def superglue_match(kp: torch.Tensor, scores: torch.Tensor, desc: torch.Tensor, counts: torch.Tensor,
                     image_hw: torch.Tensor, pairs: torch.Tensor, weights: torch.Tensor, n_layers: int = 18,
                     sinkhorn_iters: int = 20, match_threshold: float = 0.2,

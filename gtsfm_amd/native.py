@@ -79,6 +79,10 @@ BA_INPUT_STATS_FIELDS = ("components", "cameras_kept", "tracks_kept", "measureme
 MVS_VIEWS_STATS_FIELDS = ("valid_cameras", "source_views", "cameras_without_depth", "score_terms")
 MVS_FUSE_COUNT_FIELDS = ("geometric_pixels", "confidence_pixels", "joint_pixels", "reprojection_errors")
 MVS_SCORE_SCALE = 2.0 ** 40  # gtsfm_mvs_select_views' scores are integers in units of 2^-40
+GTSFM_D2NET_STAGE_TRUNK = 0  # gtsfm_d2net_stages' last_stage
+GTSFM_D2NET_STAGE_DILATED = 1
+GTSFM_D2NET_STAGE_DETECT = 2
+GTSFM_D2NET_STAGE_DESCRIBE = 3
 PATCHMATCHNET_INIT_BINS = 48  # inverse-depth bins of the random initialisation (gtsfm_patchmatchnet_batched)
 
 
@@ -138,6 +142,18 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_size_t,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_d2net_weights_floats": (c_size_t, []),
+    "gtsfm_d2net_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gtsfm_d2net_batched": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_size_t, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_d2net_stages": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_size_t, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     ),
     "gtsfm_superglue_weights_floats": (c_size_t, [c_int]),
     "gtsfm_superglue_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -18,6 +18,8 @@
  *                              gtsfm/frontend/inlier_support_processor.py:39-95 run_inlier_support
  *   gtsfm_sift_*            <- gtsfm/frontend/detector_descriptor/sift.py:27-56 detect_and_describe
  *                              (cv.cvtColor RGB2GRAY + cv.SIFT_create().detectAndCompute + Keypoints.get_top_k)
+ *   gtsfm_d2net_*           <- gtsfm/frontend/detector_descriptor/d2net.py:47-88 detect_and_describe +
+ *                              thirdparty/d2net/lib/model_test.py:12-200, pyramid.py:16-146, utils.py:34-38, 77-164
  *   gtsfm_retrieval_*       <- gtsfm/retriever/netvlad_retriever.py:77-228 (similarity blocks + pairs_from_score_matrix)
  *   gtsfm_netvlad_*         <- gtsfm/frontend/global_descriptor/netvlad_global_descriptor.py:27-46 describe +
  *                              thirdparty/hloc/netvlad.py:28-71 (NetVLADLayer), :160-191 (NetVLAD.forward)
@@ -291,6 +293,63 @@ int gtsfm_superpoint_batched(const uint8_t* d_images, const uint8_t* d_masks, in
                              const float* d_weights, int max_kpts, float keypoint_threshold, int nms_radius,
                              int remove_borders, void* d_workspace, size_t workspace_bytes, float* d_xy,
                              float* d_scores, float* d_desc, int* d_count, int* d_n_detected, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * D2-Net detector-descriptor. Replaces D2NetDetDesc.detect_and_describe
+ * (gtsfm/frontend/detector_descriptor/d2net.py:47-88, USE_MULTISCALE False) after its resize_image, and what it runs:
+ * preprocess_image 'torch' (thirdparty/d2net/lib/utils.py:34-38), process_multiscale with scales = [1]
+ * (thirdparty/d2net/lib/pyramid.py:16-146), DenseFeatureExtractionModule, HardDetectionModule and
+ * HandcraftedLocalizationModule (thirdparty/d2net/lib/model_test.py:12-200), interpolate_dense_features and
+ * upscale_positions (utils.py:77-80, 89-164). GTSFM_HIP_ABI_VERSION stays 407: new symbols only.
+ * Batched over n_img same-sized images d_images[n_img][H][W][C] u8, C = 3 RGB or 1 (the gray value in all three
+ * channels, as resize_image repeats it); H, W >= 12 (a smaller image gives a map below 2 x 2: GTSFM_ERR_ARG).
+ * Network: x = ((u / 255) - mean) / std with mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225); conv3x3 3->64,
+ * 64->64, max-pool 2/2 (floor), 64->128, 128->128, max-pool 2/2, 128->256, 256->256, 256->256, average pool 2x2 stride
+ * 1, then conv3x3 with padding 2 and dilation 2: 256->512, 512->512, 512->512; ReLU after every convolution. The map F
+ * is (512, h, w), h = (H / 2) / 2 - 1, w likewise (integer divisions).
+ * d_weights: gtsfm_d2net_weights_floats() floats, per convolution l = 0..9 (state_dict keys
+ * dense_feature_extraction.model.{0,2,5,7,10,12,14,17,19,21}): W[9][cin][cout] (W[ky*3+kx][ci][co] = torch
+ * weight[co][ci][ky][kx]) then bias[cout].
+ * Detection: element (c, i, j) is a candidate iff F[c,i,j] equals the maximum over the 512 channels at (i, j) (every
+ * channel of an exact tie is tested) and the maximum of its 3x3 neighbourhood in channel c (out-of-map neighbours
+ * ignored), and with dii = F[i-1] - 2 F[i] + F[i+1], djj likewise along j, dij = 0.25 (F[i-1,j-1] - F[i-1,j+1] -
+ * F[i+1,j-1] + F[i+1,j+1]) (out-of-map neighbours 0), det = dii djj - dij^2, tr = dii + djj: det > 0 and tr^2 / det <=
+ * 7.2; and with di = 0.5 (F[i+1] - F[i-1]), dj likewise, step_i = -(djj di - dij dj) / det, step_j = -(-dij di + dii
+ * dj) / det: |step_i| < 0.5, |step_j| < 0.5, and p = (i + step_i, j + step_j) has floor(p) >= 0, ceil(p_i) < h,
+ * ceil(p_j) < w. Its score is F[c,i,j]. Candidates are listed in torch.nonzero's order (c, then i, then j); the list
+ * holds h w per image (more would take exact ties of the channel maximum at a location; d_n_candidates still counts
+ * them, the list drops those last in (i, j, c) order). The max_keypoints highest scores are kept in descending score.
+ * Deviation: equal scores are ordered by position in the candidate list (the reference's np.argsort(-scores) is not
+ * stable and leaves that order open). Descriptor: bilinear interpolation of the 512 channels at p (weights (1-a)(1-b),
+ * (1-a) b, a (1-b), a b, a = p_i - floor(p_i), b = p_j - floor(p_j), corners floor/floor, floor/ceil, ceil/floor,
+ * ceil/ceil), then x / max(||x||, 1e-12). Coordinates: ((p * 2 + 0.5) * 2 + 0.5) times fact_i (rows) and fact_j
+ * (columns), the ratios of the original to the resized shape (1 without a resize), written (x, y) = (column, row).
+ * Outputs: d_xy[n_img][max_keypoints][2], d_score[n_img][max_keypoints], d_desc[n_img][max_keypoints][512],
+ * d_count[n_img]; rows past the count are zeroed. d_n_candidates[n_img] (may be NULL): candidates before the top-k.
+ * d_dense_map (NULL in the product path): F as [n_img][h][w][512], for tests. The call allocates nothing and does not
+ * synchronise; two calls on the same input give the same bytes. fp32-accurate arithmetic (convolutions as split-bf16
+ * MFMA products): parity with the reference is a tolerance on F and exact wherever fp32 cannot flip a test.
+ * gtsfm_d2net_workspace_bytes is 0 for a shape the call does not take.
+ * ---------------------------------------------------------------------------------------------- */
+size_t gtsfm_d2net_weights_floats(void);
+
+size_t gtsfm_d2net_workspace_bytes(int n_img, int H, int W, int max_keypoints);
+
+int gtsfm_d2net_batched(const uint8_t* d_images, int n_img, int H, int W, int C, const float* d_weights,
+                        int max_keypoints, float fact_i, float fact_j, void* d_workspace, size_t workspace_bytes,
+                        float* d_xy, float* d_score, float* d_desc, int* d_count, int* d_n_candidates,
+                        float* d_dense_map, void* stream);
+
+/* Measurement hook (tools/d2net_bench.py): gtsfm_d2net_batched stopped after stage last_stage, so that a stage's time
+ * is the difference of two calls. Outputs of the stages not run are left untouched. */
+#define GTSFM_D2NET_STAGE_TRUNK 0    /* preprocessing, conv1_1 .. conv3_3, average pool */
+#define GTSFM_D2NET_STAGE_DILATED 1  /* + the three dilated convolutions (d_dense_map) */
+#define GTSFM_D2NET_STAGE_DETECT 2   /* + detection, candidate list, top-k (d_xy, d_score, d_count, d_n_candidates) */
+#define GTSFM_D2NET_STAGE_DESCRIBE 3 /* + descriptors: the whole call */
+int gtsfm_d2net_stages(const uint8_t* d_images, int n_img, int H, int W, int C, const float* d_weights,
+                       int max_keypoints, float fact_i, float fact_j, void* d_workspace, size_t workspace_bytes,
+                       float* d_xy, float* d_score, float* d_desc, int* d_count, int* d_n_candidates,
+                       float* d_dense_map, int last_stage, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * SuperGlue matcher. Replaces SuperGlueMatcher.match (gtsfm/frontend/matcher/superglue_matcher.py:43-111) and
