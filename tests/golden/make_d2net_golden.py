@@ -12,7 +12,13 @@ in its own (candidate) order for both runs: keypoints (N, 2) = (i, j) in image p
 the descriptors of every DESC_STRIDE-th keypoint (desc_rows), which keeps the file within the limit for a committed
 file. The maker asserts the non-degeneracy that tests/test_d2net_ref.py checks again.
 
-    python tests/golden/make_d2net_golden.py
+A second file, d2net_planted_ties.npz, pins exact channel ties (tests/test_d2net_planted.py): the pass-through weights
+of tests/d2net_planted.py with channels 300 and 301 exact copies of channels 0 and 1, in the same D2Net module on a
+4 x 4-block noise image with a 17 x 33 map, fp32. It holds the image and process_multiscale's keypoints (i, j) and
+scores in its own order, with the channel of every row: the detected channels of a location (the module's own
+detection mask) in ascending order, one per row of that location, which is torch.nonzero's order. No dense map.
+
+    python tests/golden/make_d2net_golden.py [random] [planted]
 """
 import os
 import sys
@@ -27,12 +33,14 @@ sys.path.insert(0, REF)
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.dirname(HERE))  # tests/ (the reference has a `tests` package of its own)
 
+import d2net_planted as dplant  # noqa: E402
 import d2net_ref as dref  # noqa: E402
 from d2net_weights import d2net_state_dict, textured_image  # noqa: E402
 
 DESC_STRIDE = 6
 # image seeds: the first of 1, 2, ... whose image has a detection rejected by each of the three later tests
 CASES = {"a": dict(seed=2, H=48, W=64, gray=False), "b": dict(seed=15, H=52, W=44, gray=True)}
+PLANTED = dict(seed=2, H4=18, W4=34)  # block grid of the planted tie case
 
 
 def reference_model(sd_np, dtype):
@@ -87,5 +95,38 @@ def main():
     print(path, os.path.getsize(path), "bytes")
 
 
+def main_planted():
+    u = dplant.noise_blocks(PLANTED["seed"], PLANTED["H4"], PLANTED["W4"])
+    image = dplant.block_image(u)
+    model = reference_model(dplant.passthrough_state_dict(dplant.channel_sources(), dplant.tie_gains()), torch.float32)
+    r = run_reference(model, image, torch.float32)
+    with torch.no_grad():
+        detected = model.detection(torch.from_numpy(r["dense"])[None])[0].numpy()
+    ij = np.round((r["kp"].astype(np.float64) - 1.5) / 4).astype(np.int64)
+    seen, chan = {}, []
+    for i, j in ij.tolist():
+        cs = np.flatnonzero(detected[:, i, j])
+        q = seen.get((i, j), 0)
+        assert q < len(cs), "more rows at a location than detected channels"
+        chan.append(cs[q])
+        seen[(i, j)] = q + 1
+    cij = np.concatenate([np.array(chan)[:, None], ij], axis=1)
+    # every detected channel of a kept location is listed, rows are in torch.nonzero order, a score is its map value
+    assert all(n == int(detected[:, i, j].sum()) for (i, j), n in seen.items())
+    assert np.all(np.lexsort((cij[:, 2], cij[:, 1], cij[:, 0])) == np.arange(len(cij)))
+    assert np.array_equal(r["dense"][cij[:, 0], cij[:, 1], cij[:, 2]], r["scores"])
+    tied = sum(n > 1 for n in seen.values())
+    print(f"planted: map {r['dense'].shape}, {len(cij)} keypoints in channels {sorted(set(chan))}, {tied} tied pairs")
+    assert tied >= 20 and set(chan) == set(dplant.TIE_CHANNELS)
+    path = os.path.join(HERE, "d2net_planted_ties.npz")
+    np.savez_compressed(path, torch_version=np.array(torch.__version__), image=image, cij=cij.astype(np.int32),
+                        kp=r["kp"].astype(np.float32), scores=r["scores"].astype(np.float32))
+    print(path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    which = sys.argv[1:] or ["random", "planted"]
+    if "random" in which:
+        main()
+    if "planted" in which:
+        main_planted()
