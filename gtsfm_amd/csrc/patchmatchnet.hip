@@ -529,6 +529,13 @@ __global__ __launch_bounds__(256) void pm_cost_kernel(const float* __restrict__ 
         for (int g = 0; g < G; ++g) sum[g] = fmaf(sim[g], wv, sum[g]);
         wsum += wv;
     }
+    // No valid source, or every view weight underflowed: the reference's 0 / 0. mlp_eval's fmaxf would turn that NaN
+    // into a finite constant cost (uniform scores, confidence 0.5), so the NaN is written as it is and reaches the
+    // view's depth and confidence.
+    if (!(wsum > 0.0f)) {
+        cost[idx] = __builtin_nanf("");
+        return;
+    }
 #pragma unroll
     for (int g = 0; g < G; ++g) sum[g] /= wsum;
     cost[idx] = mlp_eval<G>(net, sum);

@@ -1094,7 +1094,10 @@ int gtsfm_mvs_voxel_downsample(const double* d_points, const uint8_t* d_colors, 
  * symbols only.
  *
  * Every view of the batch is a reference view once; its sources are d_src_views[view][n_src], rows of the same batch
- * (an index outside [0, n_views) is skipped). Features are computed once per view.
+ * (an index outside [0, n_views) is skipped: the view's result is that of a row holding only its valid sources, in
+ * row order, bit for bit). A view whose row holds no valid source has no matching cost (the reference's weighted mean
+ * is 0 / 0): its depth and confidence are NaN everywhere, so the confidence passes no `> threshold` test, and the other
+ * views of the batch are not affected. Features are computed once per view.
  * d_images [n_views][H][W][3] uint8 RGB; H and W multiples of 8, at least 16. Cameras as for gtsfm_mvs_*: d_wRc
  * [n_views][9], d_wtc [n_views][3], d_intrinsics [n_views][3] = (f, u0, v0), float64; stage s uses the first two rows
  * of K divided by 2^s, and src_proj ref_proj^-1 is formed in fp64 from the poses (no matrix inverse) and rounded to fp32

@@ -12,6 +12,12 @@ uniform numbers of view 0 and, for view 0 as the reference view: refined depth, 
 depths and the stage-1 regression index in fp32 and fp64, and view 0's three feature maps (the fp64 run's, stored as
 fp32, which is 1e-7 against a 2e-4 check).
 
+A second file, patchmatchnet_edges_w0.npz, ties the restatement to the module on the shapes of
+tests/patchmatchnet_cases.py: for every view of cases (c) and (d) as the reference view, with its valid sources in row
+order and the batch's uniform numbers, the fp64 run's stage-1 depth (iter4), regression index and confidence at half
+resolution ([::2, ::2]: the full map is its x2 nearest copy), as float64. The inputs are not stored: the tests rebuild
+them from the seed.
+
     python tests/golden/make_patchmatchnet_golden.py [gain]
 """
 import os
@@ -28,6 +34,7 @@ sys.path.insert(0, REF)
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.dirname(HERE))  # tests/ (the reference has a `tests` package of its own)
 
+import patchmatchnet_cases as pcases  # noqa: E402
 import patchmatchnet_ref as pref  # noqa: E402
 from patchmatchnet_weights import GAIN, patchmatchnet_state_dict  # noqa: E402
 
@@ -89,14 +96,17 @@ def reference_model(sd_np, dtype):
     return model.to(dtype).eval()
 
 
-def run_reference(model, case, dtype, ref_view=0):
-    views = [ref_view] + [int(s) for s in case["src_views"][ref_view]]
+def run_reference(model, case, dtype, ref_view=0, uniform=None):
+    """uniform: the (48, H/8, W/8) numbers of ref_view; the default is the case's own (view 0's). Source indices
+    outside the batch are left out, as the kernels skip them."""
+    n = case["images"].shape[0]
+    views = [ref_view] + [int(s) for s in case["src_views"][ref_view] if 0 <= s < n]
     img = torch.from_numpy(case["images"][views].astype(np.float32) / 255.0).permute(0, 3, 1, 2).to(dtype)
     projs = pref.projection_matrices(case["wRc"][views], case["wtc"][views], case["intrinsics"][views])
     imgs = {f"stage_{s}": img[None, :, :, ::2 ** s, ::2 ** s] for s in range(4)}  # only stage_0 is read
     proj = {f"stage_{s}": torch.from_numpy(projs[s])[None].to(dtype) for s in range(4)}
     dmin, dmax = (torch.tensor([case["depth_range"][ref_view, k]], dtype=dtype) for k in (0, 1))
-    uniform = torch.from_numpy(case["uniform"])[None].to(dtype)
+    uniform = torch.from_numpy(case["uniform"] if uniform is None else uniform)[None].to(dtype)
     grabbed = {}
 
     def keep_features(module, args, output):  # called once per view, the reference view first (a hook returns None)
@@ -161,6 +171,18 @@ def main():
                 res[f"{name}__{k}_f64"] = r64[k].astype(np.float64)
     path = os.path.join(HERE, "patchmatchnet_random_w0.npz")
     np.savez_compressed(path, **res)
+    print(path, os.path.getsize(path), "bytes")
+    edges = {"gain": np.array(gain), "torch_version": np.array(torch.__version__)}
+    for name, case in pcases.cases().items():
+        uniform = pref.batch_uniform(case)
+        for v in range(case["images"].shape[0]):
+            r64 = run_reference(m64, case, torch.float64, ref_view=v, uniform=uniform[v])
+            edges[f"{name}__view{v}__iter4"] = r64["iter4"].astype(np.float64)
+            edges[f"{name}__view{v}__index"] = r64["index"].astype(np.float64)
+            edges[f"{name}__view{v}__confidence_half"] = r64["confidence"][::2, ::2].astype(np.float64)
+            print(f"case {name} view {v}: confidence std {r64['confidence'].std():.4f}")
+    path = os.path.join(HERE, "patchmatchnet_edges_w0.npz")
+    np.savez_compressed(path, **edges)
     print(path, os.path.getsize(path), "bytes")
 
 

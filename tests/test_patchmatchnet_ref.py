@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import patchmatchnet_cases as pcases
 import patchmatchnet_ref as pref
 from patchmatchnet_weights import patchmatchnet_state_dict
 from tests.conftest import GOLDEN
@@ -76,6 +77,92 @@ def test_golden_is_not_degenerate(golden, name):
     assert (np.abs(case["depth_f32"] - case["depth_f64"]) > 1e-4 * span).mean() <= 0.01
 
 
+EDGE_CASES = ("c", "d")
+EDGE_VIEWS = [(name, v) for name, n in (("c", 2), ("d", 3)) for v in range(n)]
+ALL_VIEWS = [(name, v) for name, n in (("a", 3), ("b", 5)) for v in range(n)] + EDGE_VIEWS
+DEPTHS = ["iter0", "iter1", "iter2", "iter3", "iter4", "depth"]
+
+
+@pytest.fixture(scope="module")
+def edge_cases():
+    return pcases.cases()
+
+
+@pytest.fixture(scope="module")
+def all_cases(golden, edge_cases):
+    return {**golden, **edge_cases}
+
+
+@pytest.fixture(scope="module")
+def edge_restatements(all_cases, state_dict):
+    """{(case, view): (fp32 outputs, fp64 outputs)} of the restatement, every view with its valid sources."""
+    return {(name, v): tuple(pcases.restatement(state_dict, all_cases[name], v, dtype)
+                             for dtype in (torch.float32, torch.float64)) for name, v in ALL_VIEWS}
+
+
+def test_edge_case_shapes(edge_cases):
+    c, d = edge_cases["c"], edge_cases["d"]
+    assert c["images"].shape == (2, 16, 24, 3) and d["images"].shape == (3, 136, 152, 3)
+    for case in (c, d):
+        assert case["images"].dtype == np.uint8 and case["src_views"].dtype == np.int32
+        # the views differ in intrinsics and depth range
+        assert len({tuple(r) for r in case["intrinsics"]}) == len(case["intrinsics"])
+        assert len({tuple(r) for r in case["depth_range"]}) == len(case["depth_range"])
+    assert 155 <= d["intrinsics"][:, 0].min() and d["intrinsics"][:, 0].max() <= 170
+    # the same bytes from the same seed
+    again = pcases.cases()
+    assert all(np.array_equal(again[k]["images"], edge_cases[k]["images"]) for k in EDGE_CASES)
+
+
+def test_case_d_rows_are_ragged(edge_cases):
+    """A row with a trailing -1, a row whose first valid source is not slot 0, and a row with an index >= n."""
+    case = edge_cases["d"]
+    n, rows = case["images"].shape[0], case["src_views"]
+    assert rows.shape == (3, 3)
+    valid = (rows >= 0) & (rows < n)
+    assert any(r[-1] == -1 and v[:-1].all() for r, v in zip(rows, valid))
+    assert any(r[0] == -1 and v[1:].all() for r, v in zip(rows, valid))
+    assert (rows >= n).any()
+    for v in range(n):
+        assert v not in pcases.valid_sources(case, v) and len(pcases.valid_sources(case, v)) == 2
+
+
+@pytest.mark.parametrize("name,view", ALL_VIEWS)
+def test_every_view_is_not_degenerate(all_cases, edge_restatements, name, view):
+    """Conditions on the inputs, not tolerances on any kernel, for every view of every case as the reference view (the
+    GPU tests compare them all): the fp32 restatement is finite and stays within 2.5e-5 of the view's depth range of
+    the fp64 restatement on every depth (a quarter of the 1e-4 the kernels are held to: the 4 x the project grants
+    another summation order), at most 1 % of the stage-1 pixels have a regression index within 1e-3 of an integer and
+    the confidence varies, except on (c), whose subject is not the confidence."""
+    r32, r64 = edge_restatements[name, view]
+    span = float(all_cases[name]["depth_range"][view, 1] - all_cases[name]["depth_range"][view, 0])
+    for key in DEPTHS + ["confidence"]:
+        assert np.isfinite(r32[key]).all() and np.isfinite(r64[key]).all(), key
+    for key in DEPTHS:
+        err = np.abs(r32[key].astype(np.float64) - r64[key]).max() / span
+        print(f"case {name} view {view} {key}: fp32 restatement against fp64, largest error / range {err:.3g}")
+        assert err <= 2.5e-5, key
+    index = r64["index"]
+    assert (np.abs(index - np.round(index)) < 1e-3).mean() <= 0.01
+    if name != "c":
+        assert r64["confidence"].std() >= 0.02
+
+
+@pytest.mark.parametrize("name,view", EDGE_VIEWS)
+def test_restatement_fp64_matches_reference_fp64_on_edge_cases(golden_dir, edge_restatements, name, view):
+    """tests/golden/patchmatchnet_edges_w0.npz: the reference's module in fp64 on every view of (c) and (d) with the
+    valid sources (stage-1 depth, regression index, confidence at half resolution)."""
+    r64 = edge_restatements[name, view][1]
+    with np.load(os.path.join(golden_dir, "patchmatchnet_edges_w0.npz")) as z:
+        want = {k: z[f"{name}__view{view}__{k}"] for k in ("iter4", "index", "confidence_half")}
+    assert want["iter4"].dtype == np.float64 and want["iter4"].shape == r64["iter4"].shape
+    np.testing.assert_allclose(r64["iter4"], want["iter4"], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(r64["index"], want["index"], rtol=0, atol=1e-10)
+    np.testing.assert_allclose(r64["confidence"][::2, ::2], want["confidence_half"], rtol=0, atol=1e-10)
+    # the full map is the x2 nearest copy of what was recorded
+    np.testing.assert_array_equal(r64["confidence"], r64["confidence"][::2, ::2].repeat(2, 0).repeat(2, 1))
+
+
 def test_case_b_covers_padding_and_negative_depth(golden):
     """View 4 of case (b) stands inside view 0's depth range: some of view 0's hypotheses fall behind it (the negative
     depth rule) and some in front of it project outside its image (zero padding)."""
@@ -117,8 +204,9 @@ def test_workspace_query_refuses_bad_shapes():
 
     q = native.lib().gtsfm_patchmatchnet_workspace_bytes
     assert q(3, 2, 72, 104) > 0
+    assert q(1, 1, 16, 16) > 0 and q(2, 1, 16, 24) > 0  # the smallest shapes: a 2 x 2 and a 2 x 3 stage-3 map
     for n, s, h, w in ((0, 2, 72, 104), (-1, 2, 72, 104), (3, 0, 72, 104), (3, 2, 0, 104), (3, 2, 72, -8),
-                       (3, 2, 70, 104), (3, 2, 72, 100)):
+                       (3, 2, 70, 104), (3, 2, 72, 100), (3, 2, 8, 104), (3, 2, 72, 8)):
         assert q(n, s, h, w) == 0
 
 
