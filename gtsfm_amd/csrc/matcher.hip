@@ -894,7 +894,8 @@ int launch_finalize(const void* side1, const void* side2, const float* desc, con
 hipEvent_t g_mnn_events[2] = {nullptr, nullptr};  // gtsfm_match_set_kernel_events
 
 // ---------------------------------------------------------------------------------------------
-// Float-descriptor path (GTSFM_MATCH_F16_RERANK, e.g. SuperPoint's 256-D unit vectors). An fp16 MFMA distance GEMM
+// Float-descriptor path (GTSFM_MATCH_F16_RERANK, dim <= kFlMaxDim: SuperPoint's 256-D, D2-Net's 512-D unit vectors).
+// An fp16 MFMA distance GEMM
 // shortlists each keypoint's kFlCand nearest candidates on the other side (approximate keys |b|^2 - 2 a.b, fp32
 // accumulation); fl_rerank_kernel recomputes the shortlist with exact_top2_kernel's arithmetic, in index order, and
 // certifies it: with eps a bound on |approx - exact| squared distance (fp16 rounding of both operands, fp32
@@ -904,12 +905,12 @@ hipEvent_t g_mnn_events[2] = {nullptr, nullptr};  // gtsfm_match_set_kernel_even
 // exactly. The (d1, d2, j1) per keypoint, and so the matches, are bit-identical to GTSFM_MATCH_EXACT_F32.
 // ---------------------------------------------------------------------------------------------
 constexpr int kFlCand = 8;
-constexpr int kFlRows = 64;   // train rows per LDS chunk (two 32-row MFMA tiles)
+constexpr int kFlRows = 64;   // train rows per LDS chunk (two 32-row MFMA tiles), dpad <= 256
+constexpr int kFlRowsWide = 32;  // dpad 512: one tile per chunk, so two chunks and two workgroups still fit a CU
 constexpr int kFlQ = 128;     // queries per workgroup: 4 waves x 32
-constexpr int kFlMaxDim = 256;
+constexpr int kFlMaxDim = 512;
 
-
-__host__ __device__ inline int fl_dpad(int dim) { return dim <= 64 ? 64 : dim <= 128 ? 128 : 256; }
+__host__ __device__ inline int fl_dpad(int dim) { return dim <= 64 ? 64 : dim <= 128 ? 128 : dim <= 256 ? 256 : 512; }
 __host__ __device__ inline int fl_kpad(int kmax) { return (kmax + kFlQ - 1) / kFlQ * kFlQ; }
 
 // One wave per descriptor row: fp16 form (zero-padded to dpad), fp32 squared norm (+inf for padding rows), the
@@ -965,7 +966,7 @@ __device__ __forceinline__ void fl_insert(float x, int j, float (&v)[kFlCand], i
     id[0] = lt[0] ? j : id[0];
 }
 
-template <int NV, int DP>
+template <int NV, int DP, int KR>
 __device__ __forceinline__ void fl_fetch(fl_u32x4 (&pre)[NV], float& pn, const _Float16* __restrict__ tbase,
                                          const float* __restrict__ nbase, int c0, int tid) {
 #pragma unroll
@@ -973,34 +974,37 @@ __device__ __forceinline__ void fl_fetch(fl_u32x4 (&pre)[NV], float& pn, const _
         const int vid = tid + 256 * k, row = vid / (DP / 8), c8 = vid % (DP / 8);
         pre[k] = *(const fl_u32x4*)(tbase + (size_t)(c0 + row) * DP + 8 * c8);
     }
-    if (tid < kFlRows) pn = nbase[c0 + tid];
+    if (tid < KR) pn = nbase[c0 + tid];
 }
 
-template <int NV, int DP>
+template <int NV, int DP, int KR>
 __device__ __forceinline__ void fl_stash(const fl_u32x4 (&pre)[NV], float pn, _Float16* tl, float* nbl, int buf, int tid) {
     constexpr int RS = DP + 8;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int vid = tid + 256 * k, row = vid / (DP / 8), c8 = vid % (DP / 8);
-        *(fl_u32x4*)(tl + buf * kFlRows * RS + row * RS + 8 * c8) = pre[k];
+        *(fl_u32x4*)(tl + buf * KR * RS + row * RS + 8 * c8) = pre[k];
     }
-    if (tid < kFlRows) nbl[buf * kFlRows + tid] = pn;
+    if (tid < KR) nbl[buf * KR + tid] = pn;
 }
 
 // grid (kpad / 128, P, 2 sides). Queries (image pairs[2p + side]) sit on the MFMA's N axis: lane l keeps the
 // shortlist of query l & 31 over the train rows of its half (l >> 5) of every 32-row tile; the halves merge at the end.
-// Train rows stream through LDS in double-buffered 64-row chunks (row stride dpad + 8 halfs: conflict-free b128 reads).
-template <int NS>
+// Train rows stream through LDS in double-buffered KR-row chunks (row stride dpad + 8 halfs: conflict-free b128 reads).
+// KR is 64 up to dpad 256 and 32 at dpad 512, where a 64-row chunk pair (130.5 KiB) would leave one workgroup per CU
+// and the prefetch registers would no longer fit beside the 32 resident query fragments.
+template <int NS, int KR>
 __global__ __launch_bounds__(256, 2) void fl_shortlist_kernel(const _Float16* __restrict__ form,
                                                               const float* __restrict__ norm2,
                                                               const int* __restrict__ counts,
                                                               const int* __restrict__ pairs, int n_pairs, int kpad,
                                                               int kmax, int* __restrict__ cand,
                                                               float* __restrict__ tkey) {
-    constexpr int DP = NS * 16, RS = DP + 8, NV = DP / 32;  // NV: 16-byte loads per thread per chunk
+    constexpr int DP = NS * 16, RS = DP + 8, NV = KR * DP / 2048;  // NV: 16-byte loads per thread per chunk
+    static_assert(KR % 32 == 0 && KR <= 256 && NV * 2048 == KR * DP, "whole 32-row tiles, whole loads per thread");
     extern __shared__ __attribute__((aligned(16))) unsigned char fl_smem[];
-    _Float16* tl = (_Float16*)fl_smem;                                  // [2][kFlRows * RS]
-    float* nbl = (float*)(fl_smem + 2 * kFlRows * RS * sizeof(_Float16));  // [2][kFlRows]
+    _Float16* tl = (_Float16*)fl_smem;                                  // [2][KR * RS]
+    float* nbl = (float*)(fl_smem + 2 * KR * RS * sizeof(_Float16));  // [2][KR]
     // 1-D grid, XCD-contiguous: the hardware deals consecutive workgroups to the 8 XCDs in turn, so workgroup b runs
     // logical block (b & 7) * per_xcd + (b >> 3); each XCD then walks whole (pair, side) groups of query blocks in
     // order and the group's train image is read into that XCD's L2 once, not by every XCD
@@ -1024,13 +1028,13 @@ __global__ __launch_bounds__(256, 2) void fl_shortlist_kernel(const _Float16* __
     for (int c = 0; c < kFlCand; ++c) { v[c] = __builtin_inff(); id[c] = -1; }
     const _Float16* tbase = form + (size_t)it * kpad * DP;
     const float* nbase = norm2 + (size_t)it * kpad;
-    const int n_chunks = (nt + kFlRows - 1) / kFlRows;
-    // one chunk: two 32-row MFMA tiles against the wave's 32 queries, then the top-8 epilogue per tile
+    const int n_chunks = (nt + KR - 1) / KR;
+    // one chunk: KR / 32 32-row MFMA tiles against the wave's 32 queries, then the top-8 epilogue per tile
     auto process = [&](int c, int buf) {
-        const int c0 = c * kFlRows;
-        const _Float16* tb = tl + buf * kFlRows * RS;
+        const int c0 = c * KR;
+        const _Float16* tb = tl + buf * KR * RS;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < KR / 32; ++t) {
             fl_float16 acc = {};
             const _Float16* arow = tb + (t * 32 + (l & 31)) * RS + 8 * h;
 #pragma unroll
@@ -1045,7 +1049,7 @@ __global__ __launch_bounds__(256, 2) void fl_shortlist_kernel(const _Float16* __
             const float thr = v[kFlCand - 1];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const float4 nb = *(const float4*)(nbl + buf * kFlRows + t * 32 + 8 * g + 4 * h);
+                const float4 nb = *(const float4*)(nbl + buf * KR + t * 32 + 8 * g + 4 * h);
                 kk[4 * g] = fmaf(-2.f, acc[4 * g], nb.x);
                 kk[4 * g + 1] = fmaf(-2.f, acc[4 * g + 1], nb.y);
                 kk[4 * g + 2] = fmaf(-2.f, acc[4 * g + 2], nb.z);
@@ -1066,26 +1070,45 @@ __global__ __launch_bounds__(256, 2) void fl_shortlist_kernel(const _Float16* __
             }
         }
     };
-    // register prefetch two chunks ahead (chunk c + 2 is loaded while chunk c is computed, chunk c + 1 waits in the
-    // other register set and is stashed at the end of chunk c): each load has two chunks of work to land
-    fl_u32x4 preA[NV], preB[NV];
-    float pnA = 0.f, pnB = 0.f;
-    if (n_chunks > 0) {
-        fl_fetch<NV, DP>(preA, pnA, tbase, nbase, 0, tid);
-        fl_stash<NV, DP>(preA, pnA, tl, nbl, 0, tid);
-    }
-    if (n_chunks > 1) fl_fetch<NV, DP>(preB, pnB, tbase, nbase, kFlRows, tid);
-    __syncthreads();
-    for (int c = 0; c < n_chunks; c += 2) {
-        if (c + 2 < n_chunks) fl_fetch<NV, DP>(preA, pnA, tbase, nbase, (c + 2) * kFlRows, tid);
-        process(c, 0);
-        if (c + 1 < n_chunks) fl_stash<NV, DP>(preB, pnB, tl, nbl, 1, tid);
+    if constexpr (KR == kFlRows) {
+        // register prefetch two chunks ahead (chunk c + 2 is loaded while chunk c is computed, chunk c + 1 waits in the
+        // other register set and is stashed at the end of chunk c): each load has two chunks of work to land
+        fl_u32x4 preA[NV], preB[NV];
+        float pnA = 0.f, pnB = 0.f;
+        if (n_chunks > 0) {
+            fl_fetch<NV, DP, KR>(preA, pnA, tbase, nbase, 0, tid);
+            fl_stash<NV, DP, KR>(preA, pnA, tl, nbl, 0, tid);
+        }
+        if (n_chunks > 1) fl_fetch<NV, DP, KR>(preB, pnB, tbase, nbase, KR, tid);
         __syncthreads();
-        if (c + 1 >= n_chunks) break;
-        if (c + 3 < n_chunks) fl_fetch<NV, DP>(preB, pnB, tbase, nbase, (c + 3) * kFlRows, tid);
-        process(c + 1, 1);
-        if (c + 2 < n_chunks) fl_stash<NV, DP>(preA, pnA, tl, nbl, 0, tid);
+        for (int c = 0; c < n_chunks; c += 2) {
+            if (c + 2 < n_chunks) fl_fetch<NV, DP, KR>(preA, pnA, tbase, nbase, (c + 2) * KR, tid);
+            process(c, 0);
+            if (c + 1 < n_chunks) fl_stash<NV, DP, KR>(preB, pnB, tl, nbl, 1, tid);
+            __syncthreads();
+            if (c + 1 >= n_chunks) break;
+            if (c + 3 < n_chunks) fl_fetch<NV, DP, KR>(preB, pnB, tbase, nbase, (c + 3) * KR, tid);
+            process(c + 1, 1);
+            if (c + 2 < n_chunks) fl_stash<NV, DP, KR>(preA, pnA, tl, nbl, 0, tid);
+            __syncthreads();
+        }
+    } else {
+        // dpad 512: the 32 query fragments leave room for one prefetch set, so chunk c + 1 is loaded while chunk c
+        // is computed and stashed after it; the workgroup's other waves and the CU's second workgroup cover the rest
+        fl_u32x4 pre[NV];
+        float pn = 0.f;
+        if (n_chunks > 0) {
+            fl_fetch<NV, DP, KR>(pre, pn, tbase, nbase, 0, tid);
+            fl_stash<NV, DP, KR>(pre, pn, tl, nbl, 0, tid);
+        }
         __syncthreads();
+        for (int c = 0; c < n_chunks; ++c) {
+            if (c + 1 < n_chunks) fl_fetch<NV, DP, KR>(pre, pn, tbase, nbase, (c + 1) * KR, tid);
+            process(c, c & 1);
+            // buffer (c + 1) & 1 was last read for chunk c - 1, before the previous barrier
+            if (c + 1 < n_chunks) fl_stash<NV, DP, KR>(pre, pn, tl, nbl, (c + 1) & 1, tid);
+            __syncthreads();
+        }
     }
     // merge the two halves of each query's shortlist
 #pragma unroll
@@ -1476,13 +1499,13 @@ size_t fl_layout(int n_img, int kmax, int dim, int n_pairs, size_t* off) {
     return o;
 }
 
-template <int NS>
+template <int NS, int KR>
 int launch_fl_shortlist(const _Float16* form, const float* norm2, const int* counts, const int* pairs, int n_pairs,
                         int kpad, int kmax, int* cand, float* tkey, hipStream_t stream) {
-    const size_t lds = 2 * kFlRows * (NS * 16 + 8) * sizeof(_Float16) + 2 * kFlRows * sizeof(float);
-    GTSFM_CHECK_HIP(gtsfm_set_dynamic_lds((const void*)fl_shortlist_kernel<NS>, (int)lds));
+    const size_t lds = 2 * KR * (NS * 16 + 8) * sizeof(_Float16) + 2 * KR * sizeof(float);
+    GTSFM_CHECK_HIP(gtsfm_set_dynamic_lds((const void*)fl_shortlist_kernel<NS, KR>, (int)lds));
     const dim3 grid((unsigned)((kpad / kFlQ * (size_t)n_pairs * 2 + 7) / 8 * 8));
-    hipLaunchKernelGGL(fl_shortlist_kernel<NS>, grid, dim3(256), lds, stream, form, norm2,
+    hipLaunchKernelGGL((fl_shortlist_kernel<NS, KR>), grid, dim3(256), lds, stream, form, norm2,
                        counts, pairs, n_pairs, kpad, kmax, cand, tkey);
     return hipGetLastError() == hipSuccess ? GTSFM_OK : GTSFM_ERR_HIP;
 }
@@ -1513,9 +1536,10 @@ int run_fl_match(const float* d_desc, const int* d_counts, int n_img, int kmax, 
     int rc;
     if (g_mnn_events[0]) GTSFM_CHECK_HIP(hipEventRecord(g_mnn_events[0], stream));
     switch (dpad) {
-        case 64: rc = launch_fl_shortlist<4>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
-        case 128: rc = launch_fl_shortlist<8>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
-        default: rc = launch_fl_shortlist<16>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
+        case 64: rc = launch_fl_shortlist<4, kFlRows>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
+        case 128: rc = launch_fl_shortlist<8, kFlRows>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
+        case 256: rc = launch_fl_shortlist<16, kFlRows>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
+        default: rc = launch_fl_shortlist<32, kFlRowsWide>(form, norm2, d_counts, d_pairs, n_pairs, kpad, kmax, cand, tkey, stream); break;
     }
     if (rc != GTSFM_OK) return rc;
     if (g_mnn_events[1]) GTSFM_CHECK_HIP(hipEventRecord(g_mnn_events[1], stream));

@@ -116,7 +116,7 @@ def match_pairs(desc: torch.Tensor, counts: torch.Tensor, pairs: torch.Tensor, r
             every pair exactly once, the pairs of a group sharing image i1 (pair_groups builds one).
         out: optional caller-owned (idx (P, kmax, 2) int32, count (P,) int32) to write into (no allocation: a
             pipelined caller keeps them across steps instead of cycling cross-stream blocks through the allocator).
-        stats: optional dict filled, for GTSFM_MATCH_F16_RERANK with dim <= 256, with the certificate's counts
+        stats: optional dict filled, for GTSFM_MATCH_F16_RERANK with dim <= 512, with the certificate's counts
             (gtsfm_match_rerank_stats; synchronises the stream): "keypoint_sides" (sum over pairs of both images'
             counts), "uncertified" and "uncertified_frac" (entries the fp16 shortlist did not certify, recomputed
             exactly), "tiled_frac" (entries of (pair, side)s recomputed whole by the exact tile kernel) and
@@ -150,7 +150,7 @@ def match_pairs(desc: torch.Tensor, counts: torch.Tensor, pairs: torch.Tensor, r
         0 if groups is None else groups.shape[1], -1.0 if ratio is None else float(ratio), mode, _ptr(ws),
         ws.numel(), _ptr(idx), _ptr(cnt), native.stream_handle(stream))
     native.check(rc, "gtsfm_match_batched_grouped")
-    if stats is not None and mode == native.GTSFM_MATCH_F16_RERANK and dim <= 256:
+    if stats is not None and mode == native.GTSFM_MATCH_F16_RERANK and dim <= native.GTSFM_MATCH_F16_MAX_DIM:
         unc = np.zeros(2 * n_pairs, dtype=np.int32)
         n_unc = ctypes.c_int(0)
         native.check(L.gtsfm_match_rerank_stats(_ptr(ws), ws.numel(), n_img, kmax, dim, n_pairs, ctypes.byref(n_unc),

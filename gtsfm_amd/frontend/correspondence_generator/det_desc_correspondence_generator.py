@@ -12,7 +12,8 @@ BASELINE configs run batched on the device: images of one size go through ONE ba
 batched matcher launch per chunk of pairs:
 - SIFTDetectorDescriptor + TwoWayMatcher (configs C1, C2, C4): the exact-integer fp16 MFMA distance GEMM;
 - SuperPointDetectorDescriptor + TwoWayMatcher (config C3): the F16_RERANK matcher on the float descriptors;
-- SuperPointDetectorDescriptor + SuperGlueMatcher (config C5): batched SuperGlue (superglue.hip).
+- SuperPointDetectorDescriptor + SuperGlueMatcher (config C5): batched SuperGlue (superglue.hip);
+- D2NetDetDesc + TwoWayMatcher (the reference's d2net.yaml): the F16_RERANK matcher on the 512-D descriptors.
 The reference's shipped configs wrap both plugins in caches (sift_front_end.yaml:23-33: DetectorDescriptorCacher
 around SIFT, MatcherCacher around TwoWayMatcher). Those wrappers are looked through: every image and pair is first
 answered from the cache directory under the reference's keys (detector_descriptor_cacher.py:58-69,
@@ -34,6 +35,7 @@ from gtsfm_amd.common.keypoints import Keypoints
 from gtsfm_amd.frontend.cacher.detector_descriptor_cacher import DetectorDescriptorCacher
 from gtsfm_amd.frontend.cacher.matcher_cacher import MatcherCacher
 from gtsfm_amd.frontend.correspondence_generator.correspondence_generator_base import CorrespondenceGeneratorBase
+from gtsfm_amd.frontend.detector_descriptor.d2net import D2NetDetDesc, resized_shape
 from gtsfm_amd.frontend.detector_descriptor.detector_descriptor_base import DetectorDescriptorBase
 from gtsfm_amd.frontend.detector_descriptor.sift import SIFTDetectorDescriptor, extract_group, sift_groups
 from gtsfm_amd.frontend.matcher.matcher_base import MatcherBase
@@ -126,6 +128,39 @@ def extract_superpoint_batched(detector: SuperPointDetectorDescriptor, images: S
     cnt = count.cpu().numpy()
     xy_h, sc_h = xy.cpu().numpy(), sc.cpu().numpy()
     kps = [Keypoints(coordinates=xy_h[i, : cnt[i]], scales=None, responses=sc_h[i, : cnt[i]]) for i in range(n)]
+    out = DeviceFeatures(xy, desc, count, kps)
+    out.scores = sc
+    return out
+
+
+D2NET_GROUP_BYTES = 16 << 30  # D2-Net workspace per launch
+
+
+def extract_d2net_batched(detector: D2NetDetDesc, images: Sequence[Image]) -> DeviceFeatures:
+    """gtsfm_d2net_batched per image size in workspace-bounded groups; features gathered into one padded block
+    (descending score order per image, scores kept as the keypoints' responses, as D2NetDetDesc._unpack)."""
+    dev = upload.cuda_device()
+    n, k = len(images), detector.max_keypoints
+    xy = torch.zeros((n, k, 2), dtype=torch.float32, device=dev)
+    sc = torch.zeros((n, k), dtype=torch.float32, device=dev)
+    desc = torch.zeros((n, k, 512), dtype=torch.float32, device=dev)
+    count = torch.zeros((n,), dtype=torch.int32, device=dev)
+    by_shape: Dict[tuple, List[int]] = {}
+    for i, im in enumerate(images):
+        by_shape.setdefault(tuple(im.value_array.shape), []).append(i)
+    L = native.lib()
+    for shape, idx in by_shape.items():
+        h1, w1 = resized_shape(shape[0], shape[1])[:2]  # the network runs on the resized image
+        per = max(1, int(L.gtsfm_d2net_workspace_bytes(1, h1, w1, k)))
+        g = max(1, D2NET_GROUP_BYTES // per)
+        for s0 in range(0, len(idx), g):
+            part = idx[s0: s0 + g]
+            res = detector.extract_batch([images[i].value_array for i in part], k)
+            sel = torch.tensor(part, dtype=torch.long, device=dev)
+            xy[sel], sc[sel], desc[sel], count[sel] = res.xy, res.scores, res.desc, res.count
+    cnt = count.cpu().numpy()
+    xy_h, sc_h = xy.cpu().numpy(), sc.cpu().numpy()
+    kps = [Keypoints(coordinates=xy_h[i, : cnt[i]], responses=sc_h[i, : cnt[i]]) for i in range(n)]
     out = DeviceFeatures(xy, desc, count, kps)
     out.scores = sc
     return out
@@ -247,7 +282,7 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
 
     def _batched(self) -> Optional[str]:
         """Which batched device path serves this plugin pair: 'sift', 'superpoint_twoway', 'superpoint_superglue',
-        or None (per-call)."""
+        'd2net_twoway', or None (per-call)."""
         d, _, m, _ = self._plugins()
         twoway_l2 = type(m) is TwoWayMatcher and m._distance_type is MatchingDistanceType.EUCLIDEAN
         if type(d) is SIFTDetectorDescriptor and twoway_l2:
@@ -256,14 +291,24 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
             return "superpoint_twoway"
         if type(d) is SuperPointDetectorDescriptor and type(m) is SuperGlueMatcher:
             return "superpoint_superglue"
+        if type(d) is D2NetDetDesc and twoway_l2:
+            return "d2net_twoway"
         return None
+
+    @staticmethod
+    def _extractor(path: str):
+        """(batched extraction, descriptor width) of a path; the module's functions as they are at call time."""
+        if path == "sift":
+            return extract_sift_batched, 128
+        if path == "d2net_twoway":
+            return extract_d2net_batched, 512
+        return extract_superpoint_batched, 256
 
     def _extract(self, path: str, imgs: List[Image]) -> Tuple[DeviceFeatures, List[np.ndarray]]:
         """Batched extraction of every image that the detector cache (if any) does not hold; the first 10
         descriptor rows of every image as the per-call path would hand them to the matcher cache's key."""
         d, dc, _, _ = self._plugins()
-        sift = path == "sift"
-        extract = extract_sift_batched if sift else extract_superpoint_batched
+        extract, dim = self._extractor(path)
         if dc is None:
             return extract(d, imgs), None
         hit_idx, hit_entries, miss = [], [], []
@@ -286,8 +331,8 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
                 heads[i] = dj[:10]
             parts.append((miss, fm))
         if hit_entries:
-            dim = 128 if sift else 256
-            parts.append((hit_idx, features_from_host(hit_entries, d.max_keypoints, dim, with_scores=not sift)))
+            parts.append((hit_idx, features_from_host(hit_entries, d.max_keypoints, dim,
+                                                      with_scores=path != "sift")))
             for i, (_, dsc) in zip(hit_idx, hit_entries):
                 heads[i] = np.asarray(dsc)[:10]
         if not hit_entries:
@@ -333,7 +378,8 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
     @staticmethod
     def _match_mode(path: str, feats: DeviceFeatures) -> int:
         if path != "sift":
-            # 256-D float descriptors: fp16 MFMA shortlist + certified exact re-rank (same matches as EXACT_F32)
+            # float descriptors (SuperPoint 256-D, D2-Net 512-D, both within GTSFM_MATCH_F16_MAX_DIM): fp16 MFMA
+            # shortlist + certified exact re-rank (same matches as EXACT_F32)
             return native.GTSFM_MATCH_F16_RERANK
         if getattr(feats, "from_host", False):
             # cache entries (e.g. OpenCV's descriptors written by the reference) are checked, not assumed, to be the

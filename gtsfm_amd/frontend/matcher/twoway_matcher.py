@@ -5,8 +5,9 @@ Drop-in for gtsfm/frontend/matcher/twoway_matcher.py:24-144 (TwoWayMatcher). Sam
 empty-input behaviour (`np.array([])`) and the same NaN-row filtering and index remapping (:71-85).
 
 The distance / top-2 / ratio / mutual / sort work runs in libgtsfm_hip.so (gtsfm_match_batched):
-integer-valued descriptors (SIFT) go through the fp16 MFMA distance GEMM, anything else through the exact
-fp32 kernel. Both are bit-identical to the reference semantics restated in oracle/twoway.c.
+integer-valued descriptors (SIFT) go through the exact-integer fp16 MFMA distance GEMM, other descriptors of up to
+512 dimensions (SuperPoint, D2-Net) through the fp16 MFMA shortlist with a certified exact re-rank, anything wider
+through the exact fp32 kernel. All are bit-identical to the reference semantics restated in oracle/twoway.c.
 """
 from enum import Enum
 from typing import Optional, Tuple
@@ -62,7 +63,12 @@ def match_descriptor_pair(d1: np.ndarray, d2: np.ndarray, ratio: Optional[float]
     desc = torch.from_numpy(host).to(dev)
     counts = torch.tensor([n1, n2], dtype=torch.int32, device=dev)
     pairs = torch.tensor([[0, 1]], dtype=torch.int32, device=dev)
-    idx, cnt = device.match_pairs(desc, counts, pairs, ratio, select_match_mode(d1, d2))
+    mode = select_match_mode(d1, d2)
+    if mode == native.GTSFM_MATCH_EXACT_F32 and dim <= native.GTSFM_MATCH_F16_MAX_DIM:
+        # select_match_mode stops at 256 dims; the shortlist kernel reaches GTSFM_MATCH_F16_MAX_DIM (D2-Net's 512).
+        # Every mode gives the same matches, so this is a speed choice only.
+        mode = native.GTSFM_MATCH_F16_RERANK
+    idx, cnt = device.match_pairs(desc, counts, pairs, ratio, mode)
     m = int(cnt[0].item())
     return idx[0, :m].cpu().numpy().view(np.uint32).copy()
 

@@ -37,6 +37,7 @@ GTSFM_ERR_CAPACITY = -3
 GTSFM_MATCH_EXACT_F32 = 0
 GTSFM_MATCH_INT_F16 = 1
 GTSFM_MATCH_F16_RERANK = 2
+GTSFM_MATCH_F16_MAX_DIM = 512  # wider descriptors run the EXACT_F32 kernels under F16_RERANK
 GTSFM_SAMPSON_F64 = 0
 GTSFM_SAMPSON_F32_VERIFIER = 1
 RANSAC_STATUS_OK = 0

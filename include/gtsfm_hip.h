@@ -89,11 +89,12 @@ const char* gtsfm_hip_target(void);
  *      folded into extra K columns (every accumulator is d2 + code/16, exact in any summation order), fused
  *      row/column top-2. Exact integer arithmetic: bit-identical to EXACT_F32.
  *      kmax <= 8192, dim <= 139. (EXACT_F32: kmax <= 65535.)
- * mode GTSFM_MATCH_F16_RERANK: any float descriptors with dim <= 256 (e.g. SuperPoint's 256-D unit vectors).
- *      An fp16 MFMA distance GEMM shortlists 8 candidates per keypoint and side, an exact fp32 re-rank with
- *      EXACT_F32's arithmetic recomputes them, and a rounding-error certificate proves the shortlist holds the
- *      exact top 2; uncertified keypoints (and images with |value| > 60000 or non-finite values) are rescanned
- *      exactly. Bit-identical to EXACT_F32. dim > 256 runs the EXACT_F32 kernels. kmax <= 65535.
+ * mode GTSFM_MATCH_F16_RERANK: any float descriptors with dim <= 512 (e.g. SuperPoint's 256-D and D2-Net's 512-D
+ *      unit vectors). An fp16 MFMA distance GEMM shortlists 8 candidates per keypoint and side (operands zero-padded
+ *      to 64, 128, 256 or 512 columns), an exact fp32 re-rank with EXACT_F32's arithmetic recomputes them, and a
+ *      rounding-error certificate proves the shortlist holds the exact top 2; uncertified keypoints (and images
+ *      with |value| > 60000 or non-finite values) are rescanned exactly. Bit-identical to EXACT_F32. dim > 512 runs
+ *      the EXACT_F32 kernels. kmax <= 65535.
  * ---------------------------------------------------------------------------------------------- */
 #define GTSFM_MATCH_EXACT_F32 0
 #define GTSFM_MATCH_INT_F16 1
@@ -127,7 +128,7 @@ int gtsfm_match_max_group(int kmax, int dim);
  * time that one kernel. NULL, NULL switches it off. Process-wide; not thread-safe. */
 int gtsfm_match_set_kernel_events(void* hip_event_start, void* hip_event_stop);
 
-/* Measurement hook (no reference counterpart): after a GTSFM_MATCH_F16_RERANK gtsfm_match_batched call (dim <= 256) has
+/* Measurement hook (no reference counterpart): after a GTSFM_MATCH_F16_RERANK gtsfm_match_batched call (dim <= 512) has
  * completed on `stream`, the number of (keypoint, side) entries whose fp16 shortlist was not certified (and were
  * recomputed exactly), and optionally per pair and side (h_uncertified_per_side[side * n_pairs + p], side 0 = rows of
  * i1). A (pair, side) with at least 1/32 of its keypoints uncertified is recomputed whole by the exact tile kernel,
