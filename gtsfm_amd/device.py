@@ -638,6 +638,54 @@ def superglue_log_assignment(workspace: torch.Tensor, n_pairs: int, kmax: int, p
     return out
 
 
+def lightglue_match(kp: torch.Tensor, desc: torch.Tensor, counts: torch.Tensor, image_hw: torch.Tensor,
+                    pairs: torch.Tensor, weights: torch.Tensor, n_layers: int = 9, depth_confidence: float = 0.95,
+                    filter_threshold: float = 0.1, stream: Optional[torch.cuda.Stream] = None,
+                    workspace: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """LightGlue over every pair (gtsfm_lightglue_batched).
+
+    Args: kp (n_img, kmax, 2) f32, desc (n_img, kmax, 256) f32, counts (n_img,) int32, image_hw (n_img, 2) int32
+    (H, W), pairs (P, 2) int32, weights: the packed blob. kmax must be a multiple of 64. depth_confidence <= 0
+    disables adaptive depth.
+    Returns idx (P, kmax, 2) int32 (uint32 values, i ascending), count (P,) int32, mscores0 (P, kmax) f32 and
+    exit_layer (P,) int32.
+    """
+    _check(kp, "kp", _F32)
+    n_img, kmax = kp.shape[0], kp.shape[1]
+    assert kmax % 64 == 0, f"kmax {kmax} is no multiple of 64"
+    _check(desc, "desc", _F32, shape=(n_img, kmax, 256))
+    for t, name in ((counts, "counts"), (image_hw, "image_hw"), (pairs, "pairs")):
+        _check(t, name, _I32)
+    L = native.lib()
+    _check(weights, "weights", _F32, numel=L.gtsfm_lightglue_weights_floats(n_layers))
+    P = pairs.shape[0]
+    dev = kp.device
+    idx = torch.zeros((max(P, 1), kmax, 2), dtype=torch.int32, device=dev)
+    cnt = torch.zeros((max(P, 1),), dtype=torch.int32, device=dev)
+    ms = torch.zeros((max(P, 1), kmax), dtype=torch.float32, device=dev)
+    ex = torch.zeros((max(P, 1),), dtype=torch.int32, device=dev)
+    if P > 0:
+        ws = _take_workspace(L.gtsfm_lightglue_workspace_bytes(P, kmax), dev, workspace, stream)
+        rc = L.gtsfm_lightglue_batched(_ptr(kp), _ptr(desc), _ptr(counts), _ptr(image_hw), n_img, kmax, _ptr(pairs), P,
+                                       _ptr(weights), int(n_layers), float(depth_confidence), float(filter_threshold),
+                                       _ptr(ws), ws.numel(), _ptr(idx), _ptr(cnt), _ptr(ms), _ptr(ex),
+                                       native.stream_handle(stream))
+        native.check(rc, "gtsfm_lightglue_batched")
+    return idx[:P], cnt[:P], ms[:P], ex[:P]
+
+
+def lightglue_log_assignment(workspace: torch.Tensor, n_pairs: int, kmax: int, pair: int,
+                             stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Pair `pair`'s log-assignment matrix (kmax + 1, kmax + 1) from the workspace of the lightglue_match call that
+    used `workspace` (gtsfm_lightglue_log_assignment; entries past (m + 1, n + 1) are NaN)."""
+    out = torch.empty((kmax + 1, kmax + 1), dtype=torch.float32, device=workspace.device)
+    rc = native.lib().gtsfm_lightglue_log_assignment(_ptr(workspace), workspace.numel(), n_pairs, kmax, pair, _ptr(out),
+                                                     native.stream_handle(stream))
+    native.check(rc, "gtsfm_lightglue_log_assignment")
+    return out
+
+
 def retrieval_similarity(desc: torch.Tensor, blocksize: int,
                          stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """(N, N) f32 block-upper-triangular similarity of N global descriptors (N, D) f32 on the device

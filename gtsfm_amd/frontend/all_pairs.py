@@ -102,31 +102,38 @@ class HipKernels:
 class HipSuperPointKernels(HipKernels):
     """The deep front-end (BASELINE configs C3 / C5): SuperPointDetectorDescriptor (superpoint.hip) with either
     TwoWayMatcher on its float descriptors (F16_RERANK: fp16 MFMA shortlist + certified exact re-rank; config C3) or
-    SuperGlueMatcher (superglue.hip; config C5), then the same verifier / compaction kernels.
+    SuperGlueMatcher (superglue.hip; config C5) or LightGlueMatcher (lightglue.hip; the reference's default
+    configuration), then the same verifier / compaction kernels.
 
-    superpoint_weights / superglue_weights: the packed fp32 device blobs (pack_superpoint_weights /
-    pack_superglue_weights). SuperGlue's workspace is ~59 MB per pair at 2048 keypoints, so its pair chunks are
-    capped at superglue_pair_chunk."""
+    superpoint_weights / superglue_weights / lightglue_weights: the packed fp32 device blobs (pack_superpoint_weights /
+    pack_superglue_weights / pack_lightglue_weights). SuperGlue's workspace is ~59 MB per pair at 2048 keypoints and
+    LightGlue's ~70 MB, so their pair chunks are capped at superglue_pair_chunk."""
 
     attr_dim, desc_dim = 1, 256  # SuperPoint: score per keypoint, 256-D unit descriptors
 
     def __init__(self, superpoint_weights: torch.Tensor, matcher: str = "twoway",
                  superglue_weights: Optional[torch.Tensor] = None, n_layers: int = 18, sinkhorn_iterations: int = 20,
                  match_threshold: float = 0.2, keypoint_threshold: float = 0.005, nms_radius: int = 4,
-                 remove_borders: int = 4, superglue_pair_chunk: int = 1024):
+                 remove_borders: int = 4, superglue_pair_chunk: int = 1024,
+                 lightglue_weights: Optional[torch.Tensor] = None, lightglue_layers: int = 9,
+                 depth_confidence: float = 0.95, filter_threshold: float = 0.1):
         super().__init__()
-        if matcher not in ("twoway", "superglue"):
-            raise ValueError(f"matcher must be 'twoway' or 'superglue', not {matcher!r}")
+        if matcher not in ("twoway", "superglue", "lightglue"):
+            raise ValueError(f"matcher must be 'twoway', 'superglue' or 'lightglue', not {matcher!r}")
         if matcher == "superglue" and superglue_weights is None:
             raise ValueError("the superglue matcher needs its weight blob")
+        if matcher == "lightglue" and lightglue_weights is None:
+            raise ValueError("the lightglue matcher needs its weight blob")
         self.matcher = matcher
+        self.lg_w, self.lg_layers = lightglue_weights, lightglue_layers
+        self.depth_conf, self.filter_thr = depth_confidence, filter_threshold
         self.sp_w, self.sg_w = superpoint_weights, superglue_weights
         self.n_layers, self.iters, self.match_thr = n_layers, sinkhorn_iterations, match_threshold
         self.kp_thr, self.nms, self.border = keypoint_threshold, nms_radius, remove_borders
         # float descriptors travel as f32 (no lossless narrower wire); SuperGlue also reads the keypoint scores
         self.gather = (("xy", None), ("attr", None), ("desc", None), ("count", None)) if matcher == "superglue" else \
             (("xy", None), ("desc", None), ("count", None))
-        self.max_pair_chunk = superglue_pair_chunk if matcher == "superglue" else None
+        self.max_pair_chunk = superglue_pair_chunk if matcher != "twoway" else None
         self._sg_ws: Optional[torch.Tensor] = None
 
     def extract_workspace_bytes(self, n: int, H: int, W: int, kpts: int) -> int:
@@ -144,6 +151,14 @@ class HipSuperPointKernels(HipKernels):
         if self.matcher == "twoway":
             return self._dev.match_pairs(f.desc, f.count, pairs, ratio, self._native.GTSFM_MATCH_F16_RERANK, out=out)
         kmax = f.desc.shape[1]
+        if self.matcher == "lightglue":
+            need = int(self._native.lib().gtsfm_lightglue_workspace_bytes(int(pairs.shape[0]), kmax))
+            if self._sg_ws is None or self._sg_ws.numel() < need:
+                self._sg_ws = torch.empty(need, dtype=torch.uint8, device=f.desc.device)
+            idx, cnt, _, _ = self._dev.lightglue_match(f.xy, f.desc, f.count, image_hw, pairs, self.lg_w,
+                                                       self.lg_layers, self.depth_conf, self.filter_thr,
+                                                       workspace=self._sg_ws)
+            return idx, cnt
         need = int(self._native.lib().gtsfm_superglue_workspace_bytes(int(pairs.shape[0]), kmax))
         if self._sg_ws is None or self._sg_ws.numel() < need:
             self._sg_ws = torch.empty(need, dtype=torch.uint8, device=f.desc.device)

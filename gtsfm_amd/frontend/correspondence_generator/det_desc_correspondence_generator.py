@@ -40,6 +40,7 @@ from gtsfm_amd.frontend.detector_descriptor.detector_descriptor_base import Dete
 from gtsfm_amd.frontend.detector_descriptor.sift import SIFTDetectorDescriptor, extract_group, sift_groups
 from gtsfm_amd.frontend.matcher.matcher_base import MatcherBase
 from gtsfm_amd.frontend.detector_descriptor.superpoint import SuperPointDetectorDescriptor
+from gtsfm_amd.frontend.matcher.lightglue_matcher import LightGlueMatcher
 from gtsfm_amd.frontend.matcher.superglue_matcher import MATCH_THRESHOLD, SuperGlueMatcher
 from gtsfm_amd.frontend.matcher.twoway_matcher import MatchingDistanceType, TwoWayMatcher
 import gtsfm_amd.utils.io as io_utils
@@ -207,6 +208,46 @@ def superglue_pairs_batched(matcher: SuperGlueMatcher, feats: DeviceFeatures, im
     return out
 
 
+def lightglue_pairs_batched(matcher: LightGlueMatcher, feats: DeviceFeatures, image_shapes: Sequence[tuple],
+                            image_pairs: Sequence[Tuple[int, int]], chunk: int = 1024
+                            ) -> Dict[Tuple[int, int], np.ndarray]:
+    """All pairs through gtsfm_lightglue_batched on the resident features, `chunk` pairs per launch sequence (the
+    workspace is ~70 MB per pair at 2048 keypoints); host dict in LightGlueMatcher.match's format."""
+    out: Dict[Tuple[int, int], np.ndarray] = {}
+    pairs = np.asarray(image_pairs, dtype=np.int64).reshape(-1, 2)
+    dev = feats.desc.device
+    kmax = feats.desc.shape[1]
+    kpad = (kmax + 63) // 64 * 64
+    xy, desc = feats.xy, feats.desc
+    if kpad != kmax:
+        pad = kpad - kmax
+        xy = torch.nn.functional.pad(xy, (0, 0, 0, pad))
+        desc = torch.nn.functional.pad(desc, (0, 0, 0, pad))
+    xy, desc = xy.contiguous(), desc.contiguous()
+    hw = torch.tensor([[int(s[0]), int(s[1])] for s in image_shapes], dtype=torch.int32, device=dev)
+    cnt_h = feats.count.cpu().numpy()
+    ws = None
+    for s in range(0, len(pairs), chunk):
+        blk = pairs[s: s + chunk]
+        run = blk[(cnt_h[blk[:, 0]] > 0) & (cnt_h[blk[:, 1]] > 0)] if len(blk) else blk
+        for i1, i2 in blk:
+            out[(int(i1), int(i2))] = np.zeros((0, 2), np.uint32)
+        if not len(run):
+            continue
+        need = int(native.lib().gtsfm_lightglue_workspace_bytes(len(run), kpad))
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        idx, c, _, _ = device.lightglue_match(xy, desc, feats.count, hw, torch.from_numpy(run.astype(np.int32)).to(dev),
+                                              matcher.weights(), matcher._n_layers, matcher._depth_confidence,
+                                              matcher._filter_threshold, workspace=ws)
+        c = c.cpu().numpy()
+        w = int(c.max()) if len(c) else 0
+        idx_h = idx[:, :w].cpu().numpy().view(np.uint32)
+        for j, (i1, i2) in enumerate(run):
+            out[(int(i1), int(i2))] = idx_h[j, : c[j]].copy()
+    return out
+
+
 def features_from_host(entries: Sequence[Tuple[Keypoints, np.ndarray]], kmin: int, dim: int,
                        with_scores: bool) -> DeviceFeatures:
     """Host (keypoints, descriptors) per image -> one padded device block (cache hits enter the batched path here)."""
@@ -282,7 +323,7 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
 
     def _batched(self) -> Optional[str]:
         """Which batched device path serves this plugin pair: 'sift', 'superpoint_twoway', 'superpoint_superglue',
-        'd2net_twoway', or None (per-call)."""
+        'superpoint_lightglue', 'd2net_twoway', or None (per-call)."""
         d, _, m, _ = self._plugins()
         twoway_l2 = type(m) is TwoWayMatcher and m._distance_type is MatchingDistanceType.EUCLIDEAN
         if type(d) is SIFTDetectorDescriptor and twoway_l2:
@@ -291,6 +332,8 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
             return "superpoint_twoway"
         if type(d) is SuperPointDetectorDescriptor and type(m) is SuperGlueMatcher:
             return "superpoint_superglue"
+        if type(d) is SuperPointDetectorDescriptor and type(m) is LightGlueMatcher:
+            return "superpoint_lightglue"
         if type(d) is D2NetDetDesc and twoway_l2:
             return "d2net_twoway"
         return None
@@ -367,6 +410,8 @@ class DetDescCorrespondenceGenerator(CorrespondenceGeneratorBase):
         if todo:
             if path == "superpoint_superglue":
                 got = superglue_pairs_batched(m, feats, [im.value_array.shape for im in imgs], todo)
+            elif path == "superpoint_lightglue":
+                got = lightglue_pairs_batched(m, feats, [im.value_array.shape for im in imgs], todo)
             else:
                 got = match_pairs_batched(feats, todo, m._ratio_test_threshold, self._match_mode(path, feats))
             for key in todo:

@@ -164,6 +164,14 @@ SIGNATURES = {
          c_float, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "gtsfm_superglue_log_assignment": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gtsfm_lightglue_weights_floats": (c_size_t, [c_int]),
+    "gtsfm_lightglue_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gtsfm_lightglue_batched": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_float,
+         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "gtsfm_lightglue_log_assignment": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gtsfm_retrieval_similarity": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gtsfm_retrieval_pairs": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_float, c_int, c_void_p, c_void_p,
                                       c_void_p]),

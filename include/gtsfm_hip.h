@@ -380,6 +380,42 @@ int gtsfm_superglue_batched(const float* d_kp, const float* d_scores, const floa
 int gtsfm_superglue_log_assignment(const void* d_workspace, size_t workspace_bytes, int n_pairs, int kmax, int pair,
                                    float* d_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * LightGlue matcher at SuperPoint's width. Replaces LightGlueMatcher.match
+ * (gtsfm/frontend/matcher/lightglue_matcher.py:24-93) and the network it wraps, batched over pairs: d = 256, 4 heads
+ * of 64, n_layers (9) layers of one self block (rotary position encoding) and one cross block (shared projection,
+ * both directions), LayerNorm + GELU feed-forward, adaptive depth, double-softmax assignment with matchability.
+ * Point pruning (width_confidence) is not built: the result is the never-pruned one. Parity with the authors' code
+ * and the published checkpoint is unpinned (neither is part of the reference checkout): the arithmetic is the
+ * restatement in DESIGN.md.
+ * Features of all images: d_kp[n_img][kmax][2] (x, y) float, d_desc[n_img][kmax][256], d_counts[n_img],
+ * d_image_hw[n_img][2] = (H, W); kmax a multiple of 64. Pairs d_pairs[n_pairs][2]; a pair with an empty side gives no
+ * matches without running the network. d_weights: gtsfm_lightglue_weights_floats(n_layers) floats (layout in
+ * lightglue.hip: W^T[cin][cout] per Linear, the interleaved Wqkv permuted to [q | k | v] head-major).
+ * depth_confidence <= 0 disables stopping (every pair runs n_layers layers). Outputs: matches (i, j) with i
+ * ascending in d_out_idx[n_pairs][kmax][2] uint32, counts d_out_count[n_pairs], the matching scores of image-0
+ * keypoints d_out_mscores[n_pairs][kmax] (may be NULL), and the layer each pair left the network at,
+ * d_out_exit_layer[n_pairs] (may be NULL; n_layers - 1 for a pair that never stopped). Argument errors return
+ * GTSFM_ERR_ARG. The call allocates nothing and does not synchronise.
+ * ---------------------------------------------------------------------------------------------- */
+size_t gtsfm_lightglue_weights_floats(int n_layers);
+
+/* lightglue_matcher.py:24-93: bytes of device workspace for one call over n_pairs pairs (0 for an empty shape). */
+size_t gtsfm_lightglue_workspace_bytes(int n_pairs, int kmax);
+
+/* lightglue_matcher.py:24-93: the batched match call described above. */
+int gtsfm_lightglue_batched(const float* d_kp, const float* d_desc, const int* d_counts, const int* d_image_hw,
+                            int n_img, int kmax, const int* d_pairs, int n_pairs, const float* d_weights, int n_layers,
+                            float depth_confidence, float filter_threshold, void* d_workspace, size_t workspace_bytes,
+                            uint32_t* d_out_idx, int* d_out_count, float* d_out_mscores, int* d_out_exit_layer,
+                            void* stream);
+
+/* Inspection hook (lightglue_matcher.py:24-93 keeps only the matches): after a gtsfm_lightglue_batched call, writes
+ * pair `pair`'s log-assignment matrix from that call's workspace into d_out[(kmax + 1)][(kmax + 1)]: rows 0..m,
+ * columns 0..n (the last of each being the dustbin), NaN elsewhere. Same n_pairs / kmax as the call. */
+int gtsfm_lightglue_log_assignment(const void* d_workspace, size_t workspace_bytes, int n_pairs, int kmax, int pair,
+                                   float* d_out, void* stream);
+
 /* ---- Retrieval (f3): NetVLAD global-descriptor similarity + top-k image pairs ---------------------------------- */
 
 /* Replaces NetVLADRetriever.compute_similarity_matrix (gtsfm/retriever/netvlad_retriever.py:77-107) together with
