@@ -12,6 +12,8 @@
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 #define GTSFM_CHECK_HIP(expr)                          \
     do {                                               \
@@ -65,6 +67,29 @@ __device__ __forceinline__ int ld_int(const int* p) {
 }
 __device__ __forceinline__ void st_int(int* p, int v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// x = h + m + l exactly, each plane the bf16 rounding of what the planes above it leave (both subtractions are
+// exact): the operand split of the fp32-accurate bf16 MFMA products (conv3.hpp, sg_kernels.hpp).
+__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
+    h = (__bf16)x;
+    const float r = x - (float)h;
+    m = (__bf16)r;
+    l = (__bf16)(r - (float)m);
+}
+
+// Sum / maximum of a float over the 64 lanes, every lane getting the result: the xor butterfly from offset 32 down
+// to 1, an order the bit-exact tests of its callers depend on. (The double-precision wave sums of ba2.hip and
+// transavg.hip have orders of their own, which their oracles restate.)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
 }
 
 // Lane-wise min/max/median of three unsigned keys (v_min_u32 / v_med3_u32).

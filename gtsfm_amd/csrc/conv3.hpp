@@ -1,7 +1,19 @@
-// Implicit-GEMM 3x3 / 1x1 convolution on the bf16 matrix cores at fp32 accuracy (three-plane split products), shared
-// by SuperPoint's encoder and heads (superpoint.hip) and NetVLAD's VGG16 backbone (netvlad.hip). Included inside each
-// translation unit's anonymous namespace.
+// The convolution plumbing of the three conv nets of the deep front end: SuperPoint's encoder and heads
+// (superpoint.hip), NetVLAD's VGG16 backbone (netvlad.hip) and D2-Net's VGG16 trunk with its dilated conv4
+// (d2net.hip). One definition each of
+// - conv3_kernel: implicit-GEMM 3x3 / 1x1 convolution on the bf16 matrix cores at fp32 accuracy (three-plane split
+//   products), with its launcher conv3_launch, the only place where the tile grid is computed;
+// - conv3_split_weights: fp32 weights -> the bf16 planes conv3_kernel stages, every layer of a network in one launch;
+// - rgb_conv1_kernel: the direct 3 -> 64 first layer of the two VGG trunks, the network's preprocessing passed in as a
+//   functor. (SuperPoint's first layer has one gray input channel and nine taps: conv1a_kernel, superpoint.hip.)
+// An ordinary header: every definition has internal linkage. It sets no fp-contract pragma (the rule of se3.hpp): the
+// three includers set contract(off) and include it after that.
 #pragma once
+#include <algorithm>
+
+#include "common.hpp"
+
+namespace {
 
 constexpr int kCinChunk = 16;
 
@@ -18,22 +30,13 @@ struct ConvArgs {
 
 // ------------------------------------------------------------------ implicit-GEMM convolution, fp32-accurate bf16
 // A wave's MFMA tile: 2 rows x 16 columns of pixels (pixel i -> row i / 16, column i % 16) x 32 output channels, on
-// v_mfma_f32_32x32x16_bf16 with the three-plane split products of superglue.hip's sg_gemm3_kernel (x = x_h + x_m + x_l in bf16; six plane products per MFMA step; the dropped ones
-// are below 2^-23 |a b|): one 16-channel tap is one MFMA k-step of 16 instead of eight 32x32x2 f32 steps. The input
-// patch is split as it is staged ([plane][pixel][16] bf16); the weights are split once per call into
-// [tap][Cin / 16][plane][cout][16] (sp_split_weights_kernel) and staged as [tap][plane][64 couts][16]. A lane's
+// v_mfma_f32_32x32x16_bf16 with the three-plane split products of sg_kernels.hpp's sg_gemm3_kernel (x = x_h + x_m +
+// x_l in bf16; six plane products per MFMA step; the dropped ones are below 2^-23 |a b|): one 16-channel tap is one
+// MFMA k-step of 16 instead of eight 32x32x2 f32 steps. The input patch is split as it is staged
+// ([plane][pixel][16] bf16); the weights are split once per call into
+// [tap][Cin / 16][plane][cout][16] (conv3_split_weights) and staged as [tap][plane][64 couts][16]. A lane's
 // 16-byte fragment (8 channels) sits in half kh ^ ((row >> 3) & 1) of its 32-byte row, so the 16 rows one ds_read_b128
 // phase touches fall on distinct banks.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void sp_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
-
 __device__ __forceinline__ int swz16(int row, int half) { return 8 * (half ^ ((row >> 3) & 1)); }
 
 // A workgroup = conv3_rp row pairs x (4 / conv3_nt) waves over conv3_rows conv rows x 32 columns x 64 output
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(conv3_threads(KS), 1) void conv3_kernel(ConvArgs a,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     __bf16 hh, mm, ll;
-                    sp_split3(pv[u][j >> 2][j & 3], hh, mm, ll);
+                    split3(pv[u][j >> 2][j & 3], hh, mm, ll);
                     h[j] = hh;
                     m[j] = mm;
                     l[j] = ll;
@@ -211,3 +214,120 @@ __global__ __launch_bounds__(conv3_threads(KS), 1) void conv3_kernel(ConvArgs a,
     }
     }
 }
+
+// The one launcher: image n's tile (ty, tx) covers conv rows 2 conv3_rp .. x 32 columns, grid y the 64-channel output
+// tiles. `w` is the layer's fp32 block [KS * KS][Cin][cout_pad] followed by its cout_pad biases, `w3` its bf16 planes
+// (conv3_split_weights). An empty map launches nothing.
+template <int KS, bool POOL, int DIL = 1>
+hipError_t conv3_launch(int n, const float* in, int Hi, int Wi, int in_cstride, int in_c0, int Cin, const float* w,
+                        int cout_pad, const __bf16* w3, float* out, int out_cstride, int out_c0, int Cout, int relu,
+                        hipStream_t stream) {
+    ConvArgs a;
+    a.in = in; a.Hi = Hi; a.Wi = Wi; a.in_cstride = in_cstride; a.in_c0 = in_c0; a.Cin = Cin;
+    a.w = w;
+    a.bias = w + (size_t)KS * KS * Cin * cout_pad;
+    a.cout_pad = cout_pad;
+    a.out = out; a.out_cstride = out_cstride; a.out_c0 = out_c0; a.Cout = Cout; a.relu = relu;
+    a.tiles_x = (Wi + 31) / 32;
+    a.tiles_y = (Hi + conv3_rows(KS) - 1) / conv3_rows(KS);
+    // pooled rows only (MaxPool2d floors; an odd last conv row is dropped): conv3_rp pooled rows per tile
+    if (POOL) a.tiles_y = (Hi / 2 + conv3_rp(KS) - 1) / conv3_rp(KS);
+    if (a.tiles_x == 0 || a.tiles_y == 0) return hipSuccess;
+    const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * n), (unsigned)((Cout + 63) / 64));
+    hipLaunchKernelGGL((conv3_kernel<KS, POOL, DIL>), grid, dim3(conv3_threads(KS)), 0, stream, a, w3);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ weight split
+// fp32 weights [tap][Cin][cout_pad] -> bf16 planes [tap][Cin / 16][plane][cout_pad][16], one thread per weight; a
+// network's layers are the jobs of one launch (blockIdx.y), the table passed by value.
+struct Conv3SplitJob {
+    const float* w;
+    __bf16* out;
+    int taps, cin, cout_pad;
+};
+constexpr int kConv3SplitJobs = 16;
+struct Conv3SplitJobs {
+    Conv3SplitJob j[kConv3SplitJobs];
+};
+
+__global__ void conv3_split_weights_kernel(Conv3SplitJobs jobs) {
+    const Conv3SplitJob jb = jobs.j[blockIdx.y];
+    const int Cin = jb.cin, Cp = jb.cout_pad;
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)jb.taps * Cin * Cp) return;
+    const int co = (int)(e % Cp), ci = (int)((e / Cp) % Cin), kk = (int)(e / ((size_t)Cp * Cin));
+    __bf16 pl[3];
+    split3(jb.w[e], pl[0], pl[1], pl[2]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+        jb.out[((((size_t)kk * (Cin / kCinChunk) + ci / kCinChunk) * 3 + p) * Cp + co) * 16 + ci % kCinChunk] = pl[p];
+}
+
+hipError_t conv3_split_weights(const Conv3SplitJob* jobs, int n_jobs, hipStream_t stream) {
+    if (n_jobs <= 0 || n_jobs > kConv3SplitJobs) return hipErrorInvalidValue;
+    Conv3SplitJobs t{};
+    size_t most = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        t.j[i] = jobs[i];
+        most = std::max(most, (size_t)jobs[i].taps * jobs[i].cin * jobs[i].cout_pad);
+    }
+    hipLaunchKernelGGL(conv3_split_weights_kernel, dim3(blocks_for(most, 256), (unsigned)n_jobs), dim3(256), 0, stream,
+                       t);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ RGB first layer: 3 -> 64 channels, direct
+// A thread per pixel: the 27 preprocessed taps ([tap][channel]; padding taps are 0, as conv2d pads the preprocessed
+// tensor), then 64 outputs of 27 fp32 FMAs each with bias and ReLU; wl = [27][64] weights and 64 biases, staged in LDS.
+// Pre()(px, C, c) is the preprocessed value of channel c of the u8 pixel at px, whose C channels are interleaved.
+template <class Pre>
+__global__ __launch_bounds__(256) void rgb_conv1_kernel(const uint8_t* __restrict__ imgs, int n, int H, int W, int C,
+                                                        const float* __restrict__ wl, Pre pre,
+                                                        float* __restrict__ out) {
+    __shared__ float w[27 * 64 + 64];
+    for (int i = threadIdx.x; i < 27 * 64 + 64; i += blockDim.x) w[i] = wl[i];
+    __syncthreads();
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)n * H * W) return;
+    const int x = (int)(pix % W);
+    const int y = (int)((pix / W) % H);
+    const int img = (int)(pix / ((size_t)W * H));
+    const uint8_t* im = imgs + (size_t)img * H * W * C;
+    float v[27];  // [tap][channel]
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int yy = y + ky - 1, xx = x + kx - 1;
+            const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const uint8_t* p = im + ((size_t)(in ? yy : 0) * W + (in ? xx : 0)) * C;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[(ky * 3 + kx) * 3 + c] = in ? pre(p, C, c) : 0.0f;
+        }
+    f32x4* o = (f32x4*)(out + pix * 64);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        f32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int co = 4 * q + e;
+            float acc = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 27; ++t) acc = __builtin_fmaf(v[t], w[t * 64 + co], acc);
+            acc = acc + w[27 * 64 + co];
+            r[e] = acc > 0.0f ? acc : 0.0f;
+        }
+        o[q] = r;
+    }
+}
+
+template <class Pre>
+hipError_t rgb_conv1_launch(const uint8_t* imgs, int n, int H, int W, int C, const float* wl, Pre pre, float* out,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(rgb_conv1_kernel<Pre>, dim3(blocks_for((size_t)n * H * W, 256)), dim3(256), 0, stream, imgs, n,
+                       H, W, C, wl, pre, out);
+    return hipGetLastError();
+}
+
+}  // namespace

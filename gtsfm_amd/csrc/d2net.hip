@@ -12,18 +12,19 @@
 //      pyramid.py:112) -> (x, y) in the input image (utils.py:77-80, pyramid.py:115-116, d2net.py:83-87).
 //
 // Kernels ("D2-Net"):
-// - d2_input_conv_kernel: the preprocessing fused into the 3 -> 64 convolution (27 fp32 FMAs per output, VALU);
-// - conv3_kernel (conv3.hpp, shared with SuperPoint and NetVLAD): the other nine convolutions as implicit GEMMs on the
-//   bf16 matrix cores at fp32 accuracy, the two max-pools fused into the epilogue; the three conv4 layers are its
-//   DIL = 2 instantiation (patch halo 2, taps two pixels apart, zero padding);
+// - rgb_conv1_kernel<D2Pre> (conv3.hpp, shared with NetVLAD): the preprocessing fused into the 3 -> 64 convolution
+//   (27 fp32 FMAs per output, VALU);
+// - conv3_kernel (conv3.hpp, shared with SuperPoint and NetVLAD, as are its launcher and weight splitter): the other
+//   nine convolutions as implicit GEMMs on the bf16 matrix cores at fp32 accuracy, the two max-pools fused into the
+//   epilogue; the three conv4 layers are its DIL = 2 instantiation (patch halo 2, taps two pixels apart, zero padding);
 // - d2_avgpool_kernel: the 2x2 stride-1 average pool, a kernel of its own (half a millisecond beside a 30 ms trunk);
 // - d2_detect_kernel: ONE pass over F, one wave per location: channel maximum, then the 3x3 tests, the Hessian, the
 //   step and the corner test only for the channels that reach the maximum. Run twice (count, emit) around a prefix
 //   scan, so no derivative tensor and no dense mask is ever written;
 // - d2_chan_count_kernel / d2_chan_emit_kernel: stable regrouping of the location-ordered list by channel, which is
 //   the reference's candidate order. Prefix scans only: no floating-point atomics, no atomics at all;
-// - d2_select_kernel (radix select on the score bits, SuperPoint's) + d2_rank_kernel (rank by counting): the
-//   max_keypoints best in descending score, equal scores by candidate position;
+// - d2_select_kernel (select.hpp's radix select on the score bits, shared with SuperPoint) + d2_rank_kernel (rank by
+//   counting): the max_keypoints best in descending score, equal scores by candidate position;
 // - d2_describe_kernel: one wave per keypoint, 8 channels per lane, so each corner is one contiguous 2 KB read.
 #include <float.h>
 
@@ -31,9 +32,10 @@
 
 #pragma clang fp contract(off)
 
-namespace {
-
 #include "conv3.hpp"
+#include "select.hpp"
+
+namespace {
 
 struct D2Conv {
     int cin, cout, pool, dil;
@@ -58,64 +60,16 @@ __host__ __device__ constexpr size_t d2_w3_offset(int l) {  // bf16 planes of co
     return o;
 }
 
-// ------------------------------------------------------------------ conv 1 with the preprocessing
+// ------------------------------------------------------------------ conv 1's preprocessing (rgb_conv1_kernel)
 // utils.py:23, 35-38: float32 image, /= 255.0 in float32, then (image - mean) / std against float64 arrays, narrowed to
-// float32 by d2net.py:71. Padding taps are 0 (conv2d pads the preprocessed tensor). C == 1: the gray value in all three
-// channels (resize_image's np.repeat, d2net.py:106-109).
-__global__ __launch_bounds__(256) void d2_input_conv_kernel(const uint8_t* __restrict__ imgs, int n, int H, int W, int C,
-                                                            const float* __restrict__ wl, float* __restrict__ out) {
-    __shared__ float w[27 * 64 + 64];
-    for (int i = threadIdx.x; i < 27 * 64 + 64; i += blockDim.x) w[i] = wl[i];
-    __syncthreads();
-    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= (size_t)n * H * W) return;
-    const int x = (int)(pix % W);
-    const int y = (int)((pix / W) % H);
-    const int img = (int)(pix / ((size_t)W * H));
-    const uint8_t* im = imgs + (size_t)img * H * W * C;
-    const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
-    float v[27];  // [tap][channel]
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-            const uint8_t* p = im + ((size_t)(in ? yy : 0) * W + (in ? xx : 0)) * C;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float t = (float)p[C == 1 ? 0 : c] / 255.0f;
-                v[(ky * 3 + kx) * 3 + c] = in ? (float)(((double)t - mean[c]) / sd[c]) : 0.0f;
-            }
-        }
-    f32x4* o = (f32x4*)(out + pix * 64);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int co = 4 * q + e;
-            float acc = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 27; ++t) acc = __builtin_fmaf(v[t], w[t * 64 + co], acc);
-            acc = acc + w[27 * 64 + co];
-            r[e] = acc > 0.0f ? acc : 0.0f;
-        }
-        o[q] = r;
+// float32 by d2net.py:71. C == 1: the gray value in all three channels (resize_image's np.repeat, d2net.py:106-109).
+struct D2Pre {
+    __device__ __forceinline__ float operator()(const uint8_t* px, int C, int c) const {
+        const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
+        const float t = (float)px[C == 1 ? 0 : c] / 255.0f;
+        return (float)(((double)t - mean[c]) / sd[c]);
     }
-}
-
-// fp32 weights [tap][Cin][Cout] -> bf16 planes [tap][Cin / 16][plane][Cout][16] (conv3.hpp's staging layout)
-__global__ void d2_split_weights_kernel(const float* __restrict__ w, int Cin, int Cout, __bf16* __restrict__ out) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)9 * Cin * Cout) return;
-    const int co = (int)(e % Cout), ci = (int)((e / Cout) % Cin), kk = (int)(e / ((size_t)Cout * Cin));
-    __bf16 pl[3];
-    sp_split3(w[e], pl[0], pl[1], pl[2]);
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-        out[((((size_t)kk * (Cin / kCinChunk) + ci / kCinChunk) * 3 + p) * Cout + co) * 16 + ci % kCinChunk] = pl[p];
-}
+};
 
 // ------------------------------------------------------------------ AvgPool2d(2, stride=1) (model_test.py:33)
 // in (n, Hi, Wi, 256) -> out (n, Hi - 1, Wi - 1, 256); a lane owns four channels of one output location; the window
@@ -201,8 +155,7 @@ __global__ __launch_bounds__(256) void d2_detect_kernel(const float* __restrict_
     float m = v[0];
 #pragma unroll
     for (int k = 1; k < 8; ++k) m = fmaxf(m, v[k]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    m = wave_max(m);
     int cnt = 0;
     float pi[8], pj[8];
     unsigned hit = 0;
@@ -240,43 +193,8 @@ __global__ __launch_bounds__(256) void d2_detect_kernel(const float* __restrict_
     }
 }
 
-// ------------------------------------------------------------------ prefix scans (compact.hip's pattern)
-constexpr int kScanThreads = 256;
-
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {
-    // 256 threads: wave-level inclusive scan, then across the 4 waves
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += sh[w];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return off + x - v;
-}
-
-// per image: poff = exclusive scan of pcnt over its h w locations, ncand = the total
-__global__ __launch_bounds__(kScanThreads) void d2_scan_kernel(const int* __restrict__ pcnt, int hw,
-                                                                int* __restrict__ poff, int* __restrict__ ncand) {
-    __shared__ int sh[4];
-    const int img = blockIdx.x;
-    int carry = 0;
-    for (int base = 0; base < hw; base += kScanThreads) {
-        const int e = base + threadIdx.x;
-        const int v = e < hw ? pcnt[(size_t)img * hw + e] : 0;
-        int total;
-        const int ex = block_excl_scan(v, sh, total);
-        if (e < hw) poff[(size_t)img * hw + e] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) ncand[img] = carry;
-}
+// ------------------------------------------------------------------ prefix scans (select.hpp)
+// image_excl_scan_kernel: per image, poff = exclusive scan of pcnt over its h w locations, ncand = the total.
 
 // The location-ordered list (i, j, c) -> the reference's order (c, i, j): a stable partition by channel. Workgroup
 // (c, img) counts, then (second kernel) places, the entries of channel c in list order.
@@ -324,7 +242,7 @@ __global__ __launch_bounds__(kScanThreads) void d2_chan_emit_kernel(const D2Cand
 }
 
 // ------------------------------------------------------------------ top-k: select, then order
-// d2net.py:77 np.argsort(-scores)[:k]. Select: SuperPoint's exact radix select on the score bits (scores are > 0, so
+// d2net.py:77 np.argsort(-scores)[:k]. Select: select.hpp's exact radix select on the score bits (scores are > 0, so
 // the bits are monotone); the candidates above the k-th score and the first of those equal to it, in candidate
 // order, are kept in candidate order.
 __global__ __launch_bounds__(kScanThreads) void d2_select_kernel(const D2Cand* __restrict__ list, int cap,
@@ -336,58 +254,9 @@ __global__ __launch_bounds__(kScanThreads) void d2_select_kernel(const D2Cand* _
     const int img = blockIdx.x, tid = threadIdx.x;
     const int N = min(ncand[img], cap);
     const D2Cand* L = list + (size_t)img * cap;
-    uint32_t T = 0xFFFFFFFFu;
-    int need_eq = 0;
-    if (N > k) {
-        uint32_t prefix = 0;
-        int need = k;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            const uint32_t pmask = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-            for (int i = tid; i < 256; i += kScanThreads) histo[i] = 0;
-            __syncthreads();
-            for (int i = tid; i < N; i += kScanThreads) {
-                const uint32_t key = ~__float_as_uint(L[i].score);
-                if ((key & pmask) == (prefix & pmask)) atomicAdd(&histo[(key >> shift) & 255], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int acc = 0, d = 0;
-                for (; d < 256; ++d) {
-                    if (acc + histo[d] >= need) break;
-                    acc += histo[d];
-                }
-                pick[0] = d;
-                pick[1] = need - acc;
-            }
-            __syncthreads();
-            prefix |= (uint32_t)pick[0] << shift;
-            need = pick[1];
-            __syncthreads();
-        }
-        T = prefix;
-        need_eq = need;  // take keys < T, and the first need_eq keys == T in candidate order
-    }
-    int written = 0, eq_seen = 0;
-    for (int base = 0; base < N; base += kScanThreads) {
-        const int i = base + tid;
-        int s = 0, eq = 0;
-        D2Cand cd{};
-        if (i < N) {
-            cd = L[i];
-            const uint32_t key = ~__float_as_uint(cd.score);
-            if (N <= k || key < T) s = 1;
-            else if (key == T) eq = 1;
-        }
-        int eq_total;
-        const int eq_ex = block_excl_scan(eq, sh, eq_total);
-        if (eq && eq_seen + eq_ex < need_eq) s = 1;
-        int total;
-        const int ex = block_excl_scan(s, sh, total);
-        if (s) sel[(size_t)img * k + written + ex] = cd;
-        written += total;
-        eq_seen += eq_total;
-    }
+    const auto score_at = [&](int i) { return L[i].score; };
+    const TopkCut cut = topk_cut(N, k, histo, pick, score_at);
+    topk_emit(N, k, cut, sh, score_at, [&](int i, int o) { sel[(size_t)img * k + o] = L[i]; });
     if (tid == 0) out_count[img] = min(N, k);
 }
 
@@ -462,9 +331,7 @@ __global__ __launch_bounds__(64) void d2_describe_kernel(const float* __restrict
             ssq = __builtin_fmaf(r[half][e], r[half][e], ssq);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ssq += __shfl_xor(ssq, off);
-    const float nrm = fmaxf(__builtin_sqrtf(ssq), 1e-12f);
+    const float nrm = fmaxf(__builtin_sqrtf(wave_sum(ssq)), 1e-12f);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         f32x4 q;
@@ -521,21 +388,12 @@ bool d2_shape_ok(int n, int H, int W, int k) {
     return (size_t)kD2Dim * d.h * d.w < ((size_t)1 << 32) && (size_t)n * H * W < ((size_t)1 << 40);
 }
 
+// conv layer l of the blob (3x3, ReLU), NHWC activations of exactly its channel counts
 template <bool POOL, int DIL>
 hipError_t d2_conv(int n, const float* in, int Hi, int Wi, const float* blob, const __bf16* w3, int l, float* out,
                    hipStream_t stream) {
-    ConvArgs a;
-    a.in = in; a.Hi = Hi; a.Wi = Wi; a.in_cstride = kD2[l].cin; a.in_c0 = 0; a.Cin = kD2[l].cin;
-    a.w = blob + d2_conv_offset(l);
-    a.cout_pad = kD2[l].cout;
-    a.bias = a.w + (size_t)9 * kD2[l].cin * kD2[l].cout;
-    a.out = out; a.out_cstride = kD2[l].cout; a.out_c0 = 0; a.Cout = kD2[l].cout; a.relu = 1;
-    a.tiles_x = (Wi + 31) / 32;
-    a.tiles_y = POOL ? (Hi / 2 + conv3_rp(3) - 1) / conv3_rp(3) : (Hi + conv3_rows(3) - 1) / conv3_rows(3);
-    if (a.tiles_x == 0 || a.tiles_y == 0) return hipSuccess;
-    const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * n), (unsigned)(kD2[l].cout / 64));
-    hipLaunchKernelGGL((conv3_kernel<3, POOL, DIL>), grid, dim3(conv3_threads(3)), 0, stream, a, w3 + d2_w3_offset(l));
-    return hipGetLastError();
+    return conv3_launch<3, POOL, DIL>(n, in, Hi, Wi, kD2[l].cin, 0, kD2[l].cin, blob + d2_conv_offset(l), kD2[l].cout,
+                                      w3 + d2_w3_offset(l), out, kD2[l].cout, 0, kD2[l].cout, 1, stream);
 }
 
 }  // namespace
@@ -569,14 +427,13 @@ int gtsfm_d2net_stages(const uint8_t* d_images, int n, int H, int W, int C, cons
     __bf16* w3 = (__bf16*)(ws + L.w3);
     const float* blob = d_weights;
     // ---- trunk (model_test.py:17-33)
-    for (int l = 1; l < kD2Convs; ++l) {
-        const size_t e = (size_t)9 * kD2[l].cin * kD2[l].cout;
-        hipLaunchKernelGGL(d2_split_weights_kernel, dim3(blocks_for(e, 256)), dim3(256), 0, stream,
-                           blob + d2_conv_offset(l), kD2[l].cin, kD2[l].cout, w3 + d2_w3_offset(l));
+    {
+        Conv3SplitJob jobs[kD2Convs - 1];
+        for (int l = 1; l < kD2Convs; ++l)
+            jobs[l - 1] = {blob + d2_conv_offset(l), w3 + d2_w3_offset(l), 9, kD2[l].cin, kD2[l].cout};
+        GTSFM_CHECK_HIP(conv3_split_weights(jobs, kD2Convs - 1, stream));
     }
-    hipLaunchKernelGGL(d2_input_conv_kernel, dim3(blocks_for((size_t)n * H * W, 256)), dim3(256), 0, stream, d_images, n,
-                       H, W, C, blob + d2_conv_offset(0), A);
-    GTSFM_CHECK_HIP(hipGetLastError());
+    GTSFM_CHECK_HIP(rgb_conv1_launch(d_images, n, H, W, C, blob + d2_conv_offset(0), D2Pre{}, A, stream));
     GTSFM_CHECK_HIP((d2_conv<true, 1>(n, A, H, W, blob, w3, 1, B, stream)));
     GTSFM_CHECK_HIP((d2_conv<false, 1>(n, B, d.H2, d.W2, blob, w3, 2, A, stream)));
     GTSFM_CHECK_HIP((d2_conv<true, 1>(n, A, d.H2, d.W2, blob, w3, 3, B, stream)));
@@ -608,7 +465,7 @@ int gtsfm_d2net_stages(const uint8_t* d_images, int n, int H, int W, int C, cons
     const dim3 dgrid(blocks_for((size_t)n * hw, 4));
     hipLaunchKernelGGL((d2_detect_kernel<false>), dgrid, dim3(256), 0, stream, F, n, d.h, d.w, pcnt, (const int*)nullptr,
                        L.cap, (D2Cand*)nullptr);
-    hipLaunchKernelGGL(d2_scan_kernel, dim3(n), dim3(kScanThreads), 0, stream, (const int*)pcnt, (int)hw, poff, ncand);
+    hipLaunchKernelGGL(image_excl_scan_kernel, dim3(n), dim3(kScanThreads), 0, stream, (const int*)pcnt, (int)hw, poff, ncand);
     hipLaunchKernelGGL((d2_detect_kernel<true>), dgrid, dim3(256), 0, stream, F, n, d.h, d.w, (int*)nullptr,
                        (const int*)poff, L.cap, list1);
     hipLaunchKernelGGL(d2_chan_count_kernel, dim3(kD2Dim, n), dim3(kScanThreads), 0, stream, (const D2Cand*)list1, L.cap,

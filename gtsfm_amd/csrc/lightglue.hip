@@ -6,7 +6,8 @@
 //
 // Shared with superglue.hip (sg_kernels.hpp): the fp32-accurate split-bf16 GEMM, its weight splitter, the fused
 // attention kernel and the match emission. New here: the position encoding, the q/k/v packing with the rotary step,
-// the LayerNorm + GELU row kernel, the confidence / stop kernel and the assignment kernels.
+// the LayerNorm + GELU row kernel, the confidence / stop kernel and the assignment's log-sum-exp kernels (its argmax
+// read-out is sg_kernels.hpp's, with LgScore).
 //
 // Layout: every (pair, side) owns a kmax x C row-major block, as in superglue.hip. Adaptive depth without a host
 // read-back: `live[side]` holds the side's keypoint count while its pair is in the network and 0 afterwards. Every
@@ -38,16 +39,6 @@ __host__ __device__ constexpr size_t lg_tail(int layer) {
 }
 constexpr int kMaxLayers = 16;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 // log(sigmoid(z)) = min(z, 0) - log1p(exp(-|z|))
 __device__ __forceinline__ float log_sigmoid(float z) { return fminf(z, 0.0f) - log1pf(expf(-fabsf(z))); }
 
@@ -74,9 +65,9 @@ __global__ __launch_bounds__(256) void lg_prepare_kernel(const float* __restrict
     }
     if (i >= kmax) return;
     float* x = X + ((long)zs * kmax + i) * kD;
-    f32x4_t v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (i < n) v = *(const f32x4_t*)(desc + ((long)img * kmax + i) * kD + 4 * lane);
-    *(f32x4_t*)(x + 4 * lane) = v;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (i < n) v = *(const f32x4*)(desc + ((long)img * kmax + i) * kD + 4 * lane);
+    *(f32x4*)(x + 4 * lane) = v;
     if (lane < 32) {
         float c = 1.0f, s = 0.0f;
         if (i < n) {
@@ -167,28 +158,28 @@ __global__ __launch_bounds__(256) void lg_ln_gelu_kernel(float* __restrict__ hid
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= live[zs]) return;
     float* row = hid + ((long)zs * kmax + i) * 512;
-    f32x4_t a = *(const f32x4_t*)(row + 4 * lane), b = *(const f32x4_t*)(row + 256 + 4 * lane);
+    f32x4 a = *(const f32x4*)(row + 4 * lane), b = *(const f32x4*)(row + 256 + 4 * lane);
     const float mean = wave_sum(((a[0] + a[1]) + (a[2] + a[3])) + ((b[0] + b[1]) + (b[2] + b[3]))) / 512.0f;
     a = a - mean;
     b = b - mean;
     const float var = wave_sum(((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3])) +
                                ((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3]))) / 512.0f;
     const float inv = 1.0f / sqrtf(var + 1e-5f);
-    const f32x4_t ga = *(const f32x4_t*)(gamma + 4 * lane), gb = *(const f32x4_t*)(gamma + 256 + 4 * lane);
-    const f32x4_t ba = *(const f32x4_t*)(beta + 4 * lane), bb = *(const f32x4_t*)(beta + 256 + 4 * lane);
+    const f32x4 ga = *(const f32x4*)(gamma + 4 * lane), gb = *(const f32x4*)(gamma + 256 + 4 * lane);
+    const f32x4 ba = *(const f32x4*)(beta + 4 * lane), bb = *(const f32x4*)(beta + 256 + 4 * lane);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float ya = a[e] * inv * ga[e] + ba[e], yb = b[e] * inv * gb[e] + bb[e];
         a[e] = 0.5f * ya * (1.0f + erff(ya * 0.70710678118654752f));
         b[e] = 0.5f * yb * (1.0f + erff(yb * 0.70710678118654752f));
     }
-    *(f32x4_t*)(row + 4 * lane) = a;
-    *(f32x4_t*)(row + 256 + 4 * lane) = b;
+    *(f32x4*)(row + 4 * lane) = a;
+    *(f32x4*)(row + 256 + 4 * lane) = b;
 }
 
 // w . x + b of one 256-D row, over the wave
 __device__ __forceinline__ float row_dot(const float* __restrict__ x, const float* __restrict__ w, int lane) {
-    const f32x4_t a = *(const f32x4_t*)(x + 4 * lane), b = *(const f32x4_t*)(w + 4 * lane);
+    const f32x4 a = *(const f32x4*)(x + 4 * lane), b = *(const f32x4*)(w + 4 * lane);
     return wave_sum((a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]));
 }
 
@@ -322,71 +313,11 @@ __global__ __launch_bounds__(256) void lg_collse_kernel(const float* __restrict_
 }
 
 // the log-assignment of (i, j): log_softmax_j S + log_softmax_i S + logsigmoid(z0[i]) + logsigmoid(z1[j])
-__device__ __forceinline__ float lg_score(float s, float ui, float vj) { return (s + ui) + (s + vj); }
-
-// row-wise max / argmax over the first n columns (lowest index on ties)
-__global__ __launch_bounds__(256) void lg_rowmax_kernel(const float* __restrict__ Z,
-                                                        const int* __restrict__ side_counts, int kmax,
-                                                        const float* __restrict__ u, const float* __restrict__ v,
-                                                        float* __restrict__ max0, int* __restrict__ idx0) {
-    const int p = blockIdx.y;
-    const int m = side_counts[2 * p], n = side_counts[2 * p + 1];
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= m) return;
-    const long ld = kmax + 1;
-    const float* row = Z + (long)p * ld * ld + (long)i * ld;
-    const float ui = u[(long)p * ld + i];
-    const float* vp = v + (long)p * ld;
-    float best = -INFINITY;
-    int bj = 0x7fffffff;
-    for (int j = lane; j < n; j += 64) {
-        const float z = lg_score(row[j], ui, vp[j]);
-        if (z > best) { best = z; bj = j; }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oj = __shfl_xor(bj, o);
-        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-    }
-    if (lane == 0) {
-        max0[(long)p * kmax + i] = best;
-        idx0[(long)p * kmax + i] = bj;
-    }
-}
-
-__global__ __launch_bounds__(256) void lg_colmax_kernel(const float* __restrict__ Z,
-                                                        const int* __restrict__ side_counts, int kmax,
-                                                        const float* __restrict__ u, const float* __restrict__ v,
-                                                        int* __restrict__ idx1) {
-    __shared__ float pb[4][64];
-    __shared__ int pi[4][64];
-    const int p = blockIdx.y;
-    const int m = side_counts[2 * p], n = side_counts[2 * p + 1];
-    const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + c;
-    if (blockIdx.x * 64 >= n) return;
-    const long ld = kmax + 1;
-    const float* Zp = Z + (long)p * ld * ld;
-    const float* up = u + (long)p * ld;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    if (j < n) {
-        const float vj = v[(long)p * ld + j];
-        for (int i = g; i < m; i += 4) {
-            const float z = lg_score(Zp[(long)i * ld + j], up[i], vj);
-            if (z > best) { best = z; bi = i; }
-        }
-    }
-    pb[g][c] = best;
-    pi[g][c] = bi;
-    __syncthreads();
-    if (g == 0 && j < n) {
-        for (int o = 1; o < 4; ++o)
-            if (pb[o][c] > best || (pb[o][c] == best && pi[o][c] < bi)) { best = pb[o][c]; bi = pi[o][c]; }
-        idx1[(long)p * kmax + j] = bi;
-    }
-}
+// (assign_rowmax_kernel / assign_colmax_kernel, sg_kernels.hpp)
+struct LgScore {
+    __device__ __forceinline__ LgScore(int, int) {}
+    __device__ __forceinline__ float operator()(float s, float ui, float vj) const { return (s + ui) + (s + vj); }
+};
 
 // one pair's (m + 1) x (n + 1) log-assignment with its dustbin column / row, NaN elsewhere (ld = kmax + 1)
 __global__ __launch_bounds__(256) void lg_final_kernel(const float* __restrict__ Z, const int* __restrict__ side_counts,
@@ -400,7 +331,7 @@ __global__ __launch_bounds__(256) void lg_final_kernel(const float* __restrict__
     const int i = (int)(e / ld), j = (int)(e % ld);
     float r = __builtin_nanf("");
     if (m > 0 && n > 0 && i <= m && j <= n) {
-        if (i < m && j < n) r = lg_score(Z[(long)p * ld * ld + e], u[(long)p * ld + i], v[(long)p * ld + j]);
+        if (i < m && j < n) r = LgScore(m, n)(Z[(long)p * ld * ld + e], u[(long)p * ld + i], v[(long)p * ld + j]);
         else if (i < m) r = lsn[(long)(2 * p) * kmax + i];
         else if (j < n) r = lsn[(long)(2 * p + 1) * kmax + j];
         else r = 0.0f;
@@ -606,10 +537,8 @@ int gtsfm_lightglue_batched(const float* d_kp, const float* d_desc, const int* d
                        (const int*)side_counts, kmax, (const float*)lsp, u);
     hipLaunchKernelGGL(lg_collse_kernel, dim3(kmax / 64, n_pairs), dim3(256), 0, stream, (const float*)Z,
                        (const int*)side_counts, kmax, (const float*)lsp, v);
-    hipLaunchKernelGGL(lg_rowmax_kernel, dim3(kmax / 4, n_pairs), dim3(256), 0, stream, (const float*)Z,
-                       (const int*)side_counts, kmax, (const float*)u, (const float*)v, max0, idx0);
-    hipLaunchKernelGGL(lg_colmax_kernel, dim3(kmax / 64, n_pairs), dim3(256), 0, stream, (const float*)Z,
-                       (const int*)side_counts, kmax, (const float*)u, (const float*)v, idx1);
+    GTSFM_CHECK_HIP(hipGetLastError());
+    GTSFM_CHECK_HIP(run_assign_argmax<LgScore>(Z, side_counts, kmax, n_pairs, u, v, max0, idx0, idx1, stream));
     hipLaunchKernelGGL(sg_emit_kernel, dim3(n_pairs), dim3(256), 0, stream, (const int*)side_counts, kmax,
                        (const float*)max0, (const int*)idx0, (const int*)idx1, filter_threshold, d_out_idx,
                        d_out_count, d_out_mscores);

@@ -9,9 +9,11 @@
 //   -> whitening Linear 32768 -> 4096 + bias, L2 (:189-191).
 //
 // Kernels ("NetVLAD"):
-// - nv_input_conv_kernel: the preprocessing fused into the first 3 -> 64 conv (27 fp32 FMAs per output, VALU);
-// - conv3_kernel (conv3.hpp, shared with SuperPoint): the other 12 convolutions as implicit GEMMs on the bf16
-//   matrix cores at fp32 accuracy (three-plane split), max-pool fused into the epilogue;
+// - rgb_conv1_kernel<NvPre> (conv3.hpp, shared with D2-Net): the preprocessing fused into the first 3 -> 64 conv (27
+//   fp32 FMAs per output, VALU);
+// - conv3_kernel (conv3.hpp, shared with SuperPoint and D2-Net, as are its launcher and weight splitter): the other 12
+//   convolutions as implicit GEMMs on the bf16 matrix cores at fp32 accuracy (three-plane split), max-pool fused into
+//   the epilogue;
 // - nv_prenorm_kernel: one wave per location, the normalised features with a trailing 1 (the assignment mass);
 // - gemm_f32_kernel: strided, batched, split-K fp32 MFMA GEMM (v_mfma_f32_32x32x2f32) for the three products
 //   (assignment logits, residual sums including the masses, whitening);
@@ -23,9 +25,9 @@
 
 #pragma clang fp contract(off)
 
-namespace {
-
 #include "conv3.hpp"
+
+namespace {
 
 struct VggConv {
     int cin, cout, pool;
@@ -60,66 +62,18 @@ __host__ __device__ constexpr size_t nv_w3_offset(int l) {  // bf16 planes of co
     return o;
 }
 
-// ------------------------------------------------------------------ conv 1 with the preprocessing
+// ------------------------------------------------------------------ conv 1's preprocessing (rgb_conv1_kernel)
 // v = clamp(fl(fl(u / 255) * 255), 0, 255) - mean[c] exactly as the reference's two tensor ops (describe()'s / 255
-// and forward()'s * 255, clamp, - mean, / 1); padding taps are 0 (conv2d pads the preprocessed tensor).
-__global__ __launch_bounds__(256) void nv_input_conv_kernel(const uint8_t* __restrict__ imgs, int n, int H, int W,
-                                                            const float* __restrict__ blob, float* __restrict__ out) {
-    __shared__ float w[27 * 64 + 64];
-    const float* wl = blob + nv_conv_offset(0);
-    for (int i = threadIdx.x; i < 27 * 64 + 64; i += blockDim.x) w[i] = wl[i];
-    __syncthreads();
-    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= (size_t)n * H * W) return;
-    const int x = (int)(pix % W);
-    const int y = (int)((pix / W) % H);
-    const int img = (int)(pix / ((size_t)W * H));
-    const uint8_t* im = imgs + (size_t)img * H * W * 3;
-    const float mean[3] = {blob[0], blob[1], blob[2]};
-    float v[27];  // [tap][channel]
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-            const uint8_t* p = im + ((size_t)(in ? yy : 0) * W + (in ? xx : 0)) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float t = (float)p[c] / 255.0f;
-                t = t * 255.0f;
-                t = fminf(fmaxf(t, 0.0f), 255.0f);
-                v[(ky * 3 + kx) * 3 + c] = in ? t - mean[c] : 0.0f;
-            }
-        }
-    f32x4* o = (f32x4*)(out + pix * 64);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int co = 4 * q + e;
-            float acc = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 27; ++t) acc = __builtin_fmaf(v[t], w[t * 64 + co], acc);
-            acc = acc + w[27 * 64 + co];
-            r[e] = acc > 0.0f ? acc : 0.0f;
-        }
-        o[q] = r;
+// and forward()'s * 255, clamp, - mean, / 1); the mean is the blob's first three floats.
+struct NvPre {
+    const float* mean;
+    __device__ __forceinline__ float operator()(const uint8_t* px, int C, int c) const {
+        float t = (float)px[c] / 255.0f;
+        t = t * 255.0f;
+        t = fminf(fmaxf(t, 0.0f), 255.0f);
+        return t - mean[c];
     }
-}
-
-// fp32 weights [tap][Cin][Cout] -> bf16 planes [tap][Cin / 16][plane][Cout][16] (conv3.hpp's staging layout)
-__global__ void nv_split_weights_kernel(const float* __restrict__ w, int Cin, int Cout, __bf16* __restrict__ out) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)9 * Cin * Cout) return;
-    const int co = (int)(e % Cout), ci = (int)((e / Cout) % Cin), kk = (int)(e / ((size_t)Cout * Cin));
-    __bf16 pl[3];
-    sp_split3(w[e], pl[0], pl[1], pl[2]);
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-        out[((((size_t)kk * (Cin / kCinChunk) + ci / kCinChunk) * 3 + p) * Cout + co) * 16 + ci % kCinChunk] = pl[p];
-}
+};
 
 // ------------------------------------------------------------------ pre-normalisation (netvlad.py:187)
 // F.normalize(x, dim=1) = x / max(||x||_2, 1e-12), one wave per location (8 channels per lane); the output row is
@@ -136,8 +90,7 @@ __global__ __launch_bounds__(256) void nv_prenorm_kernel(const float* __restrict
     for (int j = 0; j < 4; ++j) ss = __builtin_fmaf(a[j], a[j], ss);
 #pragma unroll
     for (int j = 0; j < 4; ++j) ss = __builtin_fmaf(b[j], b[j], ss);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    ss = wave_sum(ss);
     const float nrm = fmaxf(__builtin_sqrtf(ss), 1e-12f);
     f32x4* dst = (f32x4*)(xa + loc * kXaStride) + 2 * lane;
     f32x4 ra, rb;
@@ -252,13 +205,9 @@ __global__ __launch_bounds__(256) void nv_softmax_kernel(float* __restrict__ s, 
     const int lane = threadIdx.x & 63;
     if (loc >= n_loc) return;
     float v = s[loc * kClusters + lane];
-    float mx = v;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    const float mx = wave_max(v);
     const float e = expf(v - mx);
-    float sum = e;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    const float sum = wave_sum(e);
     s[loc * kClusters + lane] = e / sum;
 }
 
@@ -295,8 +244,7 @@ __global__ __launch_bounds__(256) void nv_vlad_finalize_kernel(const float* __re
         const float v = resid(q + 4 * j) / cn;
         s2 = __builtin_fmaf(v, v, s2);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off);
+    s2 = wave_sum(s2);
     if ((t & 63) == 0) tot[q] = s2;
     __syncthreads();
     const float gn = fmaxf(__builtin_sqrtf(((tot[0] + tot[1]) + tot[2]) + tot[3]), 1e-12f);
@@ -324,8 +272,7 @@ __global__ __launch_bounds__(256) void nv_white_finalize_kernel(const float* __r
         y[j] = v;
         ss = __builtin_fmaf(v, v, ss);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    ss = wave_sum(ss);
     if ((t & 63) == 0) tot[t >> 6] = ss;
     __syncthreads();
     const float nrm = fmaxf(__builtin_sqrtf(((tot[0] + tot[1]) + tot[2]) + tot[3]), 1e-12f);
@@ -370,21 +317,12 @@ NvLayout nv_layout(int n, const NvDims& d) {
     return L;
 }
 
+// conv layer l of the blob (3x3), NHWC activations of exactly its channel counts
 template <bool POOL>
 hipError_t nv_conv(int n, const float* in, int Hi, int Wi, const float* blob, const __bf16* w3, int l, float* out,
                    int relu, hipStream_t stream) {
-    ConvArgs a;
-    a.in = in; a.Hi = Hi; a.Wi = Wi; a.in_cstride = kVgg[l].cin; a.in_c0 = 0; a.Cin = kVgg[l].cin;
-    a.w = blob + nv_conv_offset(l);
-    a.cout_pad = kVgg[l].cout;
-    a.bias = a.w + (size_t)9 * kVgg[l].cin * kVgg[l].cout;
-    a.out = out; a.out_cstride = kVgg[l].cout; a.out_c0 = 0; a.Cout = kVgg[l].cout; a.relu = relu;
-    a.tiles_x = (Wi + 31) / 32;
-    a.tiles_y = POOL ? (Hi / 2 + conv3_rp(3) - 1) / conv3_rp(3) : (Hi + conv3_rows(3) - 1) / conv3_rows(3);
-    if (a.tiles_x == 0 || a.tiles_y == 0) return hipSuccess;
-    const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * n), (unsigned)(kVgg[l].cout / 64));
-    hipLaunchKernelGGL((conv3_kernel<3, POOL>), grid, dim3(conv3_threads(3)), 0, stream, a, w3 + nv_w3_offset(l));
-    return hipGetLastError();
+    return conv3_launch<3, POOL>(n, in, Hi, Wi, kVgg[l].cin, 0, kVgg[l].cin, blob + nv_conv_offset(l), kVgg[l].cout,
+                                 w3 + nv_w3_offset(l), out, kVgg[l].cout, 0, kVgg[l].cout, relu, stream);
 }
 
 }  // namespace
@@ -418,19 +356,14 @@ int gtsfm_netvlad_batched(const uint8_t* d_images, int n, int H, int W, int C, c
     float* vlad = d_vlad ? d_vlad : (float*)(ws + L.vlad);
     float* wpart = (float*)(ws + L.wpart);
     const float* blob = d_weights;
-    for (int l = 1; l < kNvConvs; ++l) {
-        const size_t e = (size_t)9 * kVgg[l].cin * kVgg[l].cout;
-        hipLaunchKernelGGL(nv_split_weights_kernel, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, stream,
-                           blob + nv_conv_offset(l), kVgg[l].cin, kVgg[l].cout, w3 + nv_w3_offset(l));
-    }
-    GTSFM_CHECK_HIP(hipGetLastError());
-    // backbone (netvlad.py:183): ping-pong act0 / act1, pools after conv 2, 4, 7, 10; no ReLU after conv 13
     {
-        const size_t pix = (size_t)n * H * W;
-        hipLaunchKernelGGL(nv_input_conv_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, stream, d_images, n,
-                           H, W, blob, act0);
-        GTSFM_CHECK_HIP(hipGetLastError());
+        Conv3SplitJob jobs[kNvConvs - 1];
+        for (int l = 1; l < kNvConvs; ++l)
+            jobs[l - 1] = {blob + nv_conv_offset(l), w3 + nv_w3_offset(l), 9, kVgg[l].cin, kVgg[l].cout};
+        GTSFM_CHECK_HIP(conv3_split_weights(jobs, kNvConvs - 1, stream));
     }
+    // backbone (netvlad.py:183): ping-pong act0 / act1, pools after conv 2, 4, 7, 10; no ReLU after conv 13
+    GTSFM_CHECK_HIP(rgb_conv1_launch(d_images, n, H, W, C, blob + nv_conv_offset(0), NvPre{blob}, act0, stream));
     float* cur = act0;
     float* nxt = act1;
     int lvl = 0;

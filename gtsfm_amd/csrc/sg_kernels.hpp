@@ -1,6 +1,7 @@
 // The pieces of the attention matchers that superglue.hip and lightglue.hip share: the batched GEMMs (fp32 MFMA, and
 // the fp32-accurate split-bf16 one with its weight splitter and q/k/v epilogue), the fused flash-style attention for
-// four heads of 64, and the host-side launchers. Every definition has internal linkage: each translation unit that
+// four heads of 64, the read-out of the assignment matrix (row / column argmax, match emission), and the host-side
+// launchers. Every definition has internal linkage: each translation unit that
 // includes this header compiles the kernels it launches.
 #pragma once
 #include <float.h>
@@ -12,8 +13,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kD = 256;     // descriptor_dim
 constexpr int kHeads = 4;
@@ -69,10 +68,10 @@ __global__ __launch_bounds__(kGemmThreads) void sg_gemm_kernel(GemmArgs g) {
             const int idx = tid + kGemmThreads * it;
             const int row = idx / (kKc / 4), q = idx % (kKc / 4);
             const int gm = m0 + row, gk = k0 + 4 * q;
-            f32x4_t v = {0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
             if (gm < g.M && gk < g.K) {
-                if (gk < g.Ksplit) v = *(const f32x4_t*)(A + (long)gm * g.lda + gk);
-                else v = *(const f32x4_t*)(A2 + (long)gm * g.lda2 + (gk - g.Ksplit));
+                if (gk < g.Ksplit) v = *(const f32x4*)(A + (long)gm * g.lda + gk);
+                else v = *(const f32x4*)(A2 + (long)gm * g.lda2 + (gk - g.Ksplit));
             }
             float* d = As + row * (kKc + 1) + 4 * q;
             d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
@@ -84,14 +83,14 @@ __global__ __launch_bounds__(kGemmThreads) void sg_gemm_kernel(GemmArgs g) {
             if (!g.b_trans) {
                 const int kk = idx >> 4, q = idx & 15;
                 const int gn = n0 + 4 * q;
-                f32x4_t v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (gn < g.N && k0 + kk < g.K) v = *(const f32x4_t*)(B + (long)(k0 + kk) * g.ldb + gn);
-                *(f32x4_t*)(Bs + kk * 64 + 4 * q) = v;
+                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (gn < g.N && k0 + kk < g.K) v = *(const f32x4*)(B + (long)(k0 + kk) * g.ldb + gn);
+                *(f32x4*)(Bs + kk * 64 + 4 * q) = v;
             } else {
                 const int nn = idx / (kKc / 4), q = idx % (kKc / 4);
                 const int gn = n0 + nn;
-                f32x4_t v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (gn < g.N && k0 + 4 * q < g.K) v = *(const f32x4_t*)(B + (long)gn * g.ldb + k0 + 4 * q);
+                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (gn < g.N && k0 + 4 * q < g.K) v = *(const f32x4*)(B + (long)gn * g.ldb + k0 + 4 * q);
                 Bs[(4 * q + 0) * 64 + nn] = v[0];
                 Bs[(4 * q + 1) * 64 + nn] = v[1];
                 Bs[(4 * q + 2) * 64 + nn] = v[2];
@@ -151,19 +150,10 @@ __device__ __forceinline__ void xcd_tile(int& x, int& y, int& z) {
 // staged into LDS. TM x 128 output tile per workgroup of four waves (TM / 2 x 64 each, 32 x 32 accumulators),
 // K in chunks of 16 held in LDS as [plane][row][16] bf16 (32-byte rows: a lane's 16-byte fragment read is
 // conflict-free), the next chunk in flight in registers during the MFMAs.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kG3Tile = 128;
 
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
-
 // eight consecutive fp32 -> three 16-byte planes
-__device__ __forceinline__ void split3x8(const f32x4_t& a, const f32x4_t& b, bf16x8& h, bf16x8& m, bf16x8& l) {
+__device__ __forceinline__ void split3x8(const f32x4& a, const f32x4& b, bf16x8& h, bf16x8& m, bf16x8& l) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         __bf16 hh, mm, ll;
@@ -339,18 +329,18 @@ __global__ __launch_bounds__(256, 2) void sg_gemm3_kernel(Gemm3Args g) {
         Arow[ra] = g.A + z * g.a_batch + (long)(m0 + srow + 128 * ra) * g.lda + sk;
         A2row[ra] = g.A2 ? g.A2 + z * g.a2_batch + (long)(m0 + srow + 128 * ra) * g.lda2 + sk - g.Ksplit : nullptr;
     }
-    f32x4_t pa[SLOTS][RA][2 * kU], pb[SLOTS][2 * kU];
+    f32x4 pa[SLOTS][RA][2 * kU], pb[SLOTS][2 * kU];
     u32x4 pw[SLOTS][3][kU];
     auto load = [&](int k0, auto slot) {
         constexpr int q = decltype(slot)::value;
 #pragma unroll
         for (int ra = 0; ra < RA; ++ra) {
 #pragma unroll
-            for (int u = 0; u < 2 * kU; ++u) pa[q][ra][u] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int u = 0; u < 2 * kU; ++u) pa[q][ra][u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             if (a_ok[ra]) {
                 const float* src = k0 < g.Ksplit ? Arow[ra] + k0 : A2row[ra] + k0;
 #pragma unroll
-                for (int u = 0; u < 2 * kU; ++u) pa[q][ra][u] = *(const f32x4_t*)(src + 4 * u);
+                for (int u = 0; u < 2 * kU; ++u) pa[q][ra][u] = *(const f32x4*)(src + 4 * u);
             }
         }
         if (g.Bp) {
@@ -362,11 +352,11 @@ __global__ __launch_bounds__(256, 2) void sg_gemm3_kernel(Gemm3Args g) {
                                        : u32x4{0, 0, 0, 0};
         } else {
 #pragma unroll
-            for (int u = 0; u < 2 * kU; ++u) pb[q][u] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int u = 0; u < 2 * kU; ++u) pb[q][u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             if (b_ok) {
                 const float* src = g.Bt + z * g.b_batch + (long)(n0 + srow) * g.ldb + k0 + sk;
 #pragma unroll
-                for (int u = 0; u < 2 * kU; ++u) pb[q][u] = *(const f32x4_t*)(src + 4 * u);
+                for (int u = 0; u < 2 * kU; ++u) pb[q][u] = *(const f32x4*)(src + 4 * u);
             }
         }
     };
@@ -541,8 +531,8 @@ __global__ __launch_bounds__(256, 2) void sg_gemm3d_kernel(Gemm3Args g) {
         for (int i = 0; i < WI; ++i) {
             const int row = (TM / 2) * wm + 32 * i + r;
             const int f = (row >> 2) & 3;
-            const f32x4_t lo = *(const f32x4_t*)(st + 64 * row + 16 * ((2 * hk) ^ f));
-            const f32x4_t hi = *(const f32x4_t*)(st + 64 * row + 16 * ((2 * hk + 1) ^ f));
+            const f32x4 lo = *(const f32x4*)(st + 64 * row + 16 * ((2 * hk) ^ f));
+            const f32x4 hi = *(const f32x4*)(st + 64 * row + 16 * ((2 * hk + 1) ^ f));
             bf16x8 a[3];
             split3x8(lo, hi, a[0], a[1], a[2]);
 #pragma unroll
@@ -652,18 +642,18 @@ __global__ __launch_bounds__(kAttnThreads) void sg_attention3_kernel(const float
         const float* qrow = qkv + ((long)zs * kmax + min(q0 + 16 * qt + lr, kmax - 1)) * kD + h * kHd + 8 * lq;
 #pragma unroll
         for (int s = 0; s < 2; ++s)
-            split3x8(*(const f32x4_t*)(qrow + 32 * s) * 0.125f, *(const f32x4_t*)(qrow + 32 * s + 4) * 0.125f,
+            split3x8(*(const f32x4*)(qrow + 32 * s) * 0.125f, *(const f32x4*)(qrow + 32 * s + 4) * 0.125f,
                      qf[qt][0][s], qf[qt][1][s], qf[qt][2][s]);  // q / sqrt(64): a power of two, exact before the split
     }
     // per tile: the lane's query's running max / sum; o[qt][u][j] = O[q0 + 16 qt + lr][16 u + 4 lq + j]
     float m_run[kAttnQT], l_run[kAttnQT];
-    f32x4_t o[kAttnQT][4];
+    f32x4 o[kAttnQT][4];
 #pragma unroll
     for (int qt = 0; qt < kAttnQT; ++qt) {
         m_run[qt] = -INFINITY;
         l_run[qt] = 0.0f;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) o[qt][u] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int u = 0; u < 4; ++u) o[qt][u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     const __bf16* kb = kvp + zsrc * kv_batch;                          // [3][head][kmax][64]
     const __bf16* vb = kvp + zsrc * kv_batch + (long)3 * kD * kmax;    // [3][head][64][kmax]
@@ -697,11 +687,11 @@ __global__ __launch_bounds__(kAttnThreads) void sg_attention3_kernel(const float
         const bool more = c0 + kAttnKeys < nkeys;
         if (more) load(c0 + kAttnKeys);
         // S^T = K Q^T / 8 for 64 keys (4 tiles of 16) x the wave's query tiles
-        f32x4_t s4[kAttnQT][4];
+        f32x4 s4[kAttnQT][4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
 #pragma unroll
-            for (int qt = 0; qt < kAttnQT; ++qt) s4[qt][t] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int qt = 0; qt < kAttnQT; ++qt) s4[qt][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const bf16x8 k0 = *(const bf16x8*)&Ks[buf][0][16 * t + lr][32 * s + 8 * lq];
@@ -709,7 +699,7 @@ __global__ __launch_bounds__(kAttnThreads) void sg_attention3_kernel(const float
                 const bf16x8 k2 = *(const bf16x8*)&Ks[buf][2][16 * t + lr][32 * s + 8 * lq];
 #pragma unroll
                 for (int qt = 0; qt < kAttnQT; ++qt) {
-                    f32x4_t acc = s4[qt][t];
+                    f32x4 acc = s4[qt][t];
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k2, qf[qt][0][s], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[qt][2][s], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[qt][1][s], acc, 0, 0, 0);
@@ -772,7 +762,7 @@ __global__ __launch_bounds__(kAttnThreads) void sg_attention3_kernel(const float
                 }
 #pragma unroll
                 for (int qt = 0; qt < kAttnQT; ++qt) {
-                    f32x4_t acc = o[qt][u];
+                    f32x4 acc = o[qt][u];
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v[2], pf[qt][0][s], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v[0], pf[qt][2][s], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v[1], pf[qt][1][s], acc, 0, 0, 0);
@@ -793,11 +783,94 @@ __global__ __launch_bounds__(kAttnThreads) void sg_attention3_kernel(const float
         if (q >= nq) continue;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            f32x4_t r = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 r = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             if (l_run[qt] > 0.0f) r = o[qt][u] / l_run[qt];
-            *(f32x4_t*)(ob + (long)q * 256 + 16 * u + 4 * lq) = r;
+            *(f32x4*)(ob + (long)q * 256 + 16 * u + 4 * lq) = r;
         }
     }
+}
+
+// ------------------------------------------------------------------ assignment read-out
+// Row and column argmax of a pair's log-assignment over its m x n interior. The matcher supplies the entry as a
+// functor: Score(m, n) is built once per thread and score(z, ui, vj) is the log-assignment of an entry from Z[i][j],
+// u[i] and v[j] (SuperGlue: ((z + ui) + vj) - norm; LightGlue: (z + ui) + (z + vj)). Z is (kmax + 1)^2 per pair, u and
+// v kmax + 1. Ties go to the lowest index; 0x7fffffff stands for "none yet".
+__device__ __forceinline__ void argmax_merge(float& best, int& bi, float ob, int oi) {
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+}
+
+// one wave per row: max0[i], idx0[i] over the first n columns
+template <class Score>
+__global__ __launch_bounds__(256) void assign_rowmax_kernel(const float* __restrict__ Z,
+                                                            const int* __restrict__ side_counts, int kmax,
+                                                            const float* __restrict__ u, const float* __restrict__ v,
+                                                            float* __restrict__ max0, int* __restrict__ idx0) {
+    const int p = blockIdx.y;
+    const int m = side_counts[2 * p], n = side_counts[2 * p + 1];
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= m) return;
+    const long ld = kmax + 1;
+    const float* row = Z + (long)p * ld * ld + (long)i * ld;
+    const float ui = u[(long)p * ld + i];
+    const float* vp = v + (long)p * ld;
+    const Score score(m, n);
+    float best = -INFINITY;
+    int bj = 0x7fffffff;
+    for (int j = lane; j < n; j += 64) {
+        const float z = score(row[j], ui, vp[j]);
+        if (z > best) { best = z; bj = j; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) argmax_merge(best, bj, __shfl_xor(best, o), __shfl_xor(bj, o));
+    if (lane == 0) {
+        max0[(long)p * kmax + i] = best;
+        idx0[(long)p * kmax + i] = bj;
+    }
+}
+
+// 64 columns x 4 row groups per workgroup, the groups merged through LDS: idx1[j] over the first m rows
+template <class Score>
+__global__ __launch_bounds__(256) void assign_colmax_kernel(const float* __restrict__ Z,
+                                                            const int* __restrict__ side_counts, int kmax,
+                                                            const float* __restrict__ u, const float* __restrict__ v,
+                                                            int* __restrict__ idx1) {
+    __shared__ float pb[4][64];
+    __shared__ int pi[4][64];
+    const int p = blockIdx.y;
+    const int m = side_counts[2 * p], n = side_counts[2 * p + 1];
+    const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + c;
+    if (blockIdx.x * 64 >= n) return;
+    const long ld = kmax + 1;
+    const float* Zp = Z + (long)p * ld * ld;
+    const float* up = u + (long)p * ld;
+    const Score score(m, n);
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (j < n) {
+        const float vj = v[(long)p * ld + j];
+        for (int i = g; i < m; i += 4) {
+            const float z = score(Zp[(long)i * ld + j], up[i], vj);
+            if (z > best) { best = z; bi = i; }
+        }
+    }
+    pb[g][c] = best;
+    pi[g][c] = bi;
+    __syncthreads();
+    if (g == 0 && j < n) {
+        for (int o = 1; o < 4; ++o) argmax_merge(best, bi, pb[o][c], pi[o][c]);
+        idx1[(long)p * kmax + j] = bi;
+    }
+}
+
+template <class Score>
+hipError_t run_assign_argmax(const float* Z, const int* side_counts, int kmax, int n_pairs, const float* u,
+                             const float* v, float* max0, int* idx0, int* idx1, hipStream_t stream) {
+    hipLaunchKernelGGL(assign_rowmax_kernel<Score>, dim3(kmax / 4, n_pairs), dim3(256), 0, stream, Z, side_counts, kmax,
+                       u, v, max0, idx0);
+    hipLaunchKernelGGL(assign_colmax_kernel<Score>, dim3(kmax / 64, n_pairs), dim3(256), 0, stream, Z, side_counts,
+                       kmax, u, v, idx1);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ match emission

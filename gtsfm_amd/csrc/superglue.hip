@@ -284,70 +284,12 @@ __global__ __launch_bounds__(256) void sk_vmerge_kernel(const float2* __restrict
     v[(long)p * ld + j] = log_nu - (logf(s) + mx);
 }
 
-// row-wise max / argmax of the final scores ((Z + u) + v) - norm over the first n columns (first index on ties)
-__global__ __launch_bounds__(256) void sk_rowmax_kernel(const float* __restrict__ Z, const int* __restrict__ side_counts,
-                                                        int kmax, const float* __restrict__ u,
-                                                        const float* __restrict__ v, float* __restrict__ max0,
-                                                        int* __restrict__ idx0) {
-    const int p = blockIdx.y;
-    const int m = side_counts[2 * p], n = side_counts[2 * p + 1];
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= m) return;
-    const long ld = kmax + 1;
-    const float* row = Z + (long)p * ld * ld + (long)i * ld;
-    const float ui = u[(long)p * ld + i];
-    const float* vp = v + (long)p * ld;
-    const float norm = sk_norm(m, n);
-    float best = -INFINITY;
-    int bj = 0x7fffffff;
-    for (int j = lane; j < n; j += 64) {
-        const float z = ((row[j] + ui) + vp[j]) - norm;
-        if (z > best) { best = z; bj = j; }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oj = __shfl_xor(bj, o);
-        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-    }
-    if (lane == 0) {
-        max0[(long)p * kmax + i] = best;
-        idx0[(long)p * kmax + i] = bj;
-    }
-}
-
-__global__ __launch_bounds__(256) void sk_colmax_kernel(const float* __restrict__ Z, const int* __restrict__ side_counts,
-                                                        int kmax, const float* __restrict__ u,
-                                                        const float* __restrict__ v, int* __restrict__ idx1) {
-    __shared__ float pb[4][64];
-    __shared__ int pi[4][64];
-    const int p = blockIdx.y;
-    const int m = side_counts[2 * p], n = side_counts[2 * p + 1];
-    const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + c;
-    if (blockIdx.x * 64 >= n) return;
-    const long ld = kmax + 1;
-    const float* Zp = Z + (long)p * ld * ld;
-    const float* up = u + (long)p * ld;
-    const float norm = sk_norm(m, n);
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    if (j < n) {
-        const float vj = v[(long)p * ld + j];
-        for (int i = g; i < m; i += 4) {
-            const float z = ((Zp[(long)i * ld + j] + up[i]) + vj) - norm;
-            if (z > best) { best = z; bi = i; }
-        }
-    }
-    pb[g][c] = best;
-    pi[g][c] = bi;
-    __syncthreads();
-    if (g == 0 && j < n) {
-        for (int o = 1; o < 4; ++o)
-            if (pb[o][c] > best || (pb[o][c] == best && pi[o][c] < bi)) { best = pb[o][c]; bi = pi[o][c]; }
-        idx1[(long)p * kmax + j] = bi;
-    }
-}
+// the final scores ((Z + u) + v) - norm (assign_rowmax_kernel / assign_colmax_kernel, sg_kernels.hpp)
+struct SkScore {
+    float norm;
+    __device__ __forceinline__ SkScore(int m, int n) : norm(sk_norm(m, n)) {}
+    __device__ __forceinline__ float operator()(float z, float ui, float vj) const { return ((z + ui) + vj) - norm; }
+};
 
 // final log-assignment of one pair ((Z + u) + v) - norm, rows 0..m, columns 0..n (ld = kmax + 1), NaN elsewhere
 __global__ __launch_bounds__(256) void sk_final_kernel(const float* __restrict__ Z, const int* __restrict__ side_counts,
@@ -375,27 +317,26 @@ __host__ SgLayout sg_layout(int P, int kmax) {
     SgLayout L{};
     const size_t S = (size_t)2 * P * kmax;
     const size_t ld = (size_t)kmax + 1;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += gtsfm_align_up(bytes, 256); return r; };
-    L.enc_in = take(S * 16 * 4);
-    L.X = take(S * kD * 4);
-    L.T1 = take(S * kD * 4);
-    L.T2 = take(S * kD * 4);
-    L.qkv = take(S * kD * 4);  // q only: keys and values go straight to the bf16 planes (kvp)
-    L.kvp = take(S * 2 * kD * 3 * sizeof(__bf16));  // key and value planes of the current layer
-    L.att = take(S * kD * 4);
-    L.msg = take(S * kD * 4);
-    L.hid = take(S * 512 * 4);
-    L.Z = take((size_t)P * ld * ld * 4);
-    L.u = take((size_t)P * ld * 4);
-    L.v = take((size_t)P * ld * 4);
-    L.part = take((size_t)P * sk_row_blocks(kmax) * ld * sizeof(float2));  // Sinkhorn column partials
-    L.max0 = take((size_t)P * kmax * 4);
-    L.idx0 = take((size_t)P * kmax * 4);
-    L.idx1 = take((size_t)P * kmax * 4);
-    L.cnt = take((size_t)2 * P * 4);
-    L.wsplit = take(kSplitElems * 3 * sizeof(__bf16));
-    L.total = o;
+    WsCarver c;
+    L.enc_in = c.take(S * 16 * 4);
+    L.X = c.take(S * kD * 4);
+    L.T1 = c.take(S * kD * 4);
+    L.T2 = c.take(S * kD * 4);
+    L.qkv = c.take(S * kD * 4);  // q only: keys and values go straight to the bf16 planes (kvp)
+    L.kvp = c.take(S * 2 * kD * 3 * sizeof(__bf16));  // key and value planes of the current layer
+    L.att = c.take(S * kD * 4);
+    L.msg = c.take(S * kD * 4);
+    L.hid = c.take(S * 512 * 4);
+    L.Z = c.take((size_t)P * ld * ld * 4);
+    L.u = c.take((size_t)P * ld * 4);
+    L.v = c.take((size_t)P * ld * 4);
+    L.part = c.take((size_t)P * sk_row_blocks(kmax) * ld * sizeof(float2));  // Sinkhorn column partials
+    L.max0 = c.take((size_t)P * kmax * 4);
+    L.idx0 = c.take((size_t)P * kmax * 4);
+    L.idx1 = c.take((size_t)P * kmax * 4);
+    L.cnt = c.take((size_t)2 * P * 4);
+    L.wsplit = c.take(kSplitElems * 3 * sizeof(__bf16));
+    L.total = c.o;
     return L;
 }
 
@@ -553,10 +494,7 @@ int gtsfm_superglue_batched(const float* d_kp, const float* d_scores, const floa
                                kmax, (const float*)u, v);
         }
     }
-    hipLaunchKernelGGL(sk_rowmax_kernel, dim3(kmax / 4, n_pairs), dim3(256), 0, stream, Z, side_counts, kmax, u, v,
-                       max0, idx0);
-    hipLaunchKernelGGL(sk_colmax_kernel, dim3(kmax / 64, n_pairs), dim3(256), 0, stream, Z, side_counts, kmax, u, v,
-                       idx1);
+    GTSFM_CHECK_HIP(run_assign_argmax<SkScore>(Z, side_counts, kmax, n_pairs, u, v, max0, idx0, idx1, stream));
     hipLaunchKernelGGL(sg_emit_kernel, dim3(n_pairs), dim3(256), 0, stream, side_counts, kmax, max0, idx0, idx1,
                        match_threshold, d_out_idx, d_out_count, d_out_mscores);
     GTSFM_CHECK_HIP(hipGetLastError());

@@ -12,15 +12,20 @@
 // summation order. Activations are NHWC fp32 in HBM; a workgroup stages an input patch and the 16-channel weight slab
 // in LDS (2x2 max-pool fused into the epilogue, in-lane). Everything after the convolutions is elementwise / stencil
 // work on the score map and is HBM-bound.
+//
+// Shared: the convolution, its launcher and its weight splitter with NetVLAD and D2-Net (conv3.hpp); the workgroup
+// scan, the per-image scan and the top-k selection with D2-Net (select.hpp). conv1a_kernel (one gray channel, nine
+// taps) is SuperPoint's own.
 #include <float.h>
 
 #include "common.hpp"
 
 #pragma clang fp contract(off)
 
-namespace {
+#include "conv3.hpp"
+#include "select.hpp"
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
+namespace {
 
 // ------------------------------------------------------------------ packed weight blob (include/gtsfm_hip.h)
 struct SpLayer {
@@ -70,10 +75,10 @@ __global__ __launch_bounds__(256) void conv1a_kernel(const uint8_t* __restrict__
             const int yy = y + ky - 1, xx = x + kx - 1;
             v[ky * 3 + kx] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? sp_gray(im, C, W, yy, xx) : 0.0f;
         }
-    f32x4_t* o = (f32x4_t*)(out + pix * 64);
+    f32x4* o = (f32x4*)(out + pix * 64);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        f32x4_t r;
+        f32x4 r;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int co = 4 * q + e;
@@ -87,28 +92,11 @@ __global__ __launch_bounds__(256) void conv1a_kernel(const uint8_t* __restrict__
     }
 }
 
-#include "conv3.hpp"
-
-// fp32 weights [tap][Cin][cout_pad] of layers L1B..LDB -> bf16 planes [tap][Cin / 16][plane][cout_pad][16] at
-// sp_w3_offset(layer); blockIdx.y = layer - 1
+// bf16 planes [tap][Cin / 16][plane][cout_pad][16] of layers L1B..LDB (conv3_split_weights) sit at sp_w3_offset(layer)
 __host__ __device__ constexpr size_t sp_w3_offset(int l) {
     size_t o = 0;
     for (int i = 1; i < l; ++i) o += (size_t)3 * kSp[i].k * kSp[i].k * kSp[i].cin * kSp[i].cout_pad;
     return o;
-}
-
-__global__ void sp_split_weights_kernel(const float* __restrict__ blob, __bf16* __restrict__ w3) {
-    const int l = blockIdx.y + 1;
-    const int KK = kSp[l].k * kSp[l].k, Cin = kSp[l].cin, Cp = kSp[l].cout_pad;
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)KK * Cin * Cp) return;
-    const int co = (int)(e % Cp), ci = (int)((e / Cp) % Cin), kk = (int)(e / ((size_t)Cp * Cin));
-    __bf16 pl[3];
-    sp_split3(blob[sp_layer_offset(l) + e], pl[0], pl[1], pl[2]);
-    __bf16* out = w3 + sp_w3_offset(l);
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-        out[((((size_t)kk * (Cin / kCinChunk) + ci / kCinChunk) * 3 + p) * Cp + co) * 16 + ci % kCinChunk] = pl[p];
 }
 
 // ------------------------------------------------------------------ dense scores: softmax over 65, depth-to-space
@@ -181,26 +169,6 @@ __global__ void nms_step_kernel(int stage, size_t total, const float* __restrict
 
 // ------------------------------------------------------------------ keypoint extraction in raster order
 // superpoint.py:175-184: nonzero(s > threshold) (row-major), then remove_borders (y in [b, H - b), x in [b, W - b)).
-constexpr int kRowThreads = 256;
-
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {
-    // 256 threads: wave-level inclusive scan, then across the 4 waves
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += sh[w];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return off + x - v;
-}
-
 // Image masks (gtsfm/frontend/detector_descriptor/superpoint.py:68-70, Keypoints.filter_by_mask): a detection at
 // integer pixel (x, y) survives iff mask[y][x] == 1 (the reference compares with == 1, so other nonzero values drop
 // it); masks[n][mH][mW] u8 over the full image (the detection grid, 8 * floor(H / 8) x 8 * floor(W / 8), lies inside).
@@ -208,7 +176,7 @@ __device__ __forceinline__ bool mask_ok(const uint8_t* __restrict__ masks, int i
     return masks == nullptr || masks[((size_t)img * mH + y) * mW + x] == 1;
 }
 
-__global__ __launch_bounds__(kRowThreads) void row_count_kernel(const float* __restrict__ N, int H, int W, float thr,
+__global__ __launch_bounds__(kScanThreads) void row_count_kernel(const float* __restrict__ N, int H, int W, float thr,
                                                                  int border, const uint8_t* __restrict__ masks, int mH,
                                                                  int mW, int* __restrict__ rowcnt) {
     __shared__ int sh[4];
@@ -216,31 +184,15 @@ __global__ __launch_bounds__(kRowThreads) void row_count_kernel(const float* __r
     const float* row = N + ((size_t)img * H + y) * W;
     int c = 0;
     const bool yok = y >= border && y < H - border;
-    for (int x = threadIdx.x; x < W; x += kRowThreads)
+    for (int x = threadIdx.x; x < W; x += kScanThreads)
         c += (yok && x >= border && x < W - border && row[x] > thr && mask_ok(masks, img, mH, mW, y, x)) ? 1 : 0;
     int total;
     block_excl_scan(c, sh, total);
     if (threadIdx.x == 0) rowcnt[(size_t)img * H + y] = total;
 }
 
-__global__ __launch_bounds__(kRowThreads) void row_scan_kernel(const int* __restrict__ rowcnt, int H,
-                                                                int* __restrict__ rowoff, int* __restrict__ n_det) {
-    __shared__ int sh[4];
-    const int img = blockIdx.x;
-    int carry = 0;
-    for (int base = 0; base < H; base += kRowThreads) {
-        const int y = base + threadIdx.x;
-        const int v = y < H ? rowcnt[(size_t)img * H + y] : 0;
-        int total;
-        const int ex = block_excl_scan(v, sh, total);
-        if (y < H) rowoff[(size_t)img * H + y] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) n_det[img] = carry;
-}
-
 // candidates: per image, (y * W + x) raster index and score
-__global__ __launch_bounds__(kRowThreads) void row_emit_kernel(const float* __restrict__ N, int H, int W, float thr,
+__global__ __launch_bounds__(kScanThreads) void row_emit_kernel(const float* __restrict__ N, int H, int W, float thr,
                                                                 int border, const uint8_t* __restrict__ masks, int mH,
                                                                 int mW, const int* __restrict__ rowoff, int cap,
                                                                 int* __restrict__ cand_idx,
@@ -250,7 +202,7 @@ __global__ __launch_bounds__(kRowThreads) void row_emit_kernel(const float* __re
     if (!(y >= border && y < H - border)) return;
     const float* row = N + ((size_t)img * H + y) * W;
     int off = rowoff[(size_t)img * H + y];
-    for (int base = 0; base < W; base += kRowThreads) {
+    for (int base = 0; base < W; base += kScanThreads) {
         const int x = base + threadIdx.x;
         const float s = x < W ? row[x] : 0.0f;
         const int f = (x < W && x >= border && x < W - border && s > thr && mask_ok(masks, img, mH, mW, y, x)) ? 1 : 0;
@@ -268,9 +220,7 @@ __global__ __launch_bounds__(kRowThreads) void row_emit_kernel(const float* __re
 // gtsfm's Keypoints.get_top_k (common/keypoints.py:89-110) keeps the k highest responses (np.argpartition: order
 // implementation-defined); here: exact radix select on the score bits, ties at the threshold broken by raster
 // order, selected keypoints emitted in raster order (with k >= N this is the reference's own order).
-constexpr int kTopThreads = 256;
-
-__global__ __launch_bounds__(kTopThreads) void topk_select_kernel(const int* __restrict__ cand_idx,
+__global__ __launch_bounds__(kScanThreads) void topk_select_kernel(const int* __restrict__ cand_idx,
                                                                    const float* __restrict__ cand_score, int cap,
                                                                    const int* __restrict__ n_det, int k, int W,
                                                                    float* __restrict__ out_xy,
@@ -283,84 +233,28 @@ __global__ __launch_bounds__(kTopThreads) void topk_select_kernel(const int* __r
     const int N = min(n_det[img], cap);
     const int* ci = cand_idx + (size_t)img * cap;
     const float* cs = cand_score + (size_t)img * cap;
-    const int kk = min(N, k);
-    // keys: larger score first -> order by ~bits (scores are > threshold >= 0, so the bits are monotone)
-    uint32_t T = 0xFFFFFFFFu;
-    int need_eq = 0;
-    if (N > k) {
-        uint32_t prefix = 0;
-        int need = k;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            const uint32_t pmask = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-            for (int i = tid; i < 256; i += kTopThreads) histo[i] = 0;
-            __syncthreads();
-            for (int i = tid; i < N; i += kTopThreads) {
-                const uint32_t key = ~__float_as_uint(cs[i]);
-                if ((key & pmask) == (prefix & pmask)) atomicAdd(&histo[(key >> shift) & 255], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int acc = 0, d = 0;
-                for (; d < 256; ++d) {
-                    if (acc + histo[d] >= need) break;
-                    acc += histo[d];
-                }
-                pick[0] = d;
-                pick[1] = need - acc;
-            }
-            __syncthreads();
-            prefix |= (uint32_t)pick[0] << shift;
-            need = pick[1];
-            __syncthreads();
-        }
-        T = prefix;
-        need_eq = need;  // take keys < T, and the first need_eq keys == T in raster order
-    }
-    int written = 0, eq_seen = 0;
-    for (int base = 0; base < N; base += kTopThreads) {
-        const int i = base + tid;
-        int sel = 0, eq = 0;
-        if (i < N) {
-            const uint32_t key = ~__float_as_uint(cs[i]);
-            if (N <= k || key < T) sel = 1;
-            else if (key == T) eq = 1;
-        }
-        int eq_total;
-        const int eq_ex = block_excl_scan(eq, sh, eq_total);
-        if (eq && eq_seen + eq_ex < need_eq) sel = 1;
-        int total;
-        const int ex = block_excl_scan(sel, sh, total);
-        if (sel) {
-            const int o = written + ex;
-            const int r = ci[i];
-            out_xy[((size_t)img * k + o) * 2] = (float)(r % W);
-            out_xy[((size_t)img * k + o) * 2 + 1] = (float)(r / W);
-            out_score[(size_t)img * k + o] = cs[i];
-        }
-        written += total;
-        eq_seen += eq_total;
-    }
-    if (tid == 0) out_count[img] = kk;
+    const auto score_at = [&](int i) { return cs[i]; };
+    const TopkCut cut = topk_cut(N, k, histo, pick, score_at);
+    topk_emit(N, k, cut, sh, score_at, [&](int i, int o) {
+        const int r = ci[i];
+        out_xy[((size_t)img * k + o) * 2] = (float)(r % W);
+        out_xy[((size_t)img * k + o) * 2 + 1] = (float)(r / W);
+        out_score[(size_t)img * k + o] = cs[i];
+    });
+    if (tid == 0) out_count[img] = min(N, k);
 }
 
 // ------------------------------------------------------------------ descriptors at keypoints
 // superpoint.py:196-198 + sample_descriptors (:73-91): dense map L2-normalised per cell, bilinear grid_sample at
 // ((kp - s/2 + 0.5) / (w s - s/2 - 0.5), ...) * 2 - 1 with align_corners False and zero padding, L2-normalised.
 // One wave per keypoint, 4 channels per lane.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ __launch_bounds__(64) void desc_sample_kernel(const float* __restrict__ D /*(n,H8,W8,256)*/, int H8, int W8,
                                                          const float* __restrict__ xy, const int* __restrict__ count,
                                                          int k, float* __restrict__ out /*(n,k,256)*/) {
     const int img = blockIdx.y, j = blockIdx.x, lane = threadIdx.x;
-    f32x4_t* o = (f32x4_t*)(out + ((size_t)img * k + j) * 256) + lane;
+    f32x4* o = (f32x4*)(out + ((size_t)img * k + j) * 256) + lane;
     if (j >= count[img]) {
-        *o = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        *o = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         return;
     }
     const float kx = xy[((size_t)img * k + j) * 2], ky = xy[((size_t)img * k + j) * 2 + 1];
@@ -380,20 +274,20 @@ __global__ __launch_bounds__(64) void desc_sample_kernel(const float* __restrict
     const float wsw = ((float)x1 - ix) * (iy - (float)y0);
     const float wse = (ix - (float)x0) * (iy - (float)y0);
     const float* Db = D + (size_t)img * H8 * W8 * 256;
-    auto corner = [&](int yy, int xx) -> f32x4_t {
-        if (yy < 0 || yy >= H8 || xx < 0 || xx >= W8) return f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
-        const f32x4_t v = *((const f32x4_t*)(Db + ((size_t)yy * W8 + xx) * 256) + lane);
+    auto corner = [&](int yy, int xx) -> f32x4 {
+        if (yy < 0 || yy >= H8 || xx < 0 || xx >= W8) return f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        const f32x4 v = *((const f32x4*)(Db + ((size_t)yy * W8 + xx) * 256) + lane);
         const float ss = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
         const float nrm = fmaxf(sqrtf(ss), 1e-12f);
-        return f32x4_t{v[0] / nrm, v[1] / nrm, v[2] / nrm, v[3] / nrm};
+        return f32x4{v[0] / nrm, v[1] / nrm, v[2] / nrm, v[3] / nrm};
     };
-    const f32x4_t a = corner(y0, x0), b = corner(y0, x1), c = corner(y1, x0), d = corner(y1, x1);
-    f32x4_t r;
+    const f32x4 a = corner(y0, x0), b = corner(y0, x1), c = corner(y1, x0), d = corner(y1, x1);
+    f32x4 r;
 #pragma unroll
     for (int e = 0; e < 4; ++e) r[e] = a[e] * wnw + b[e] * wne + c[e] * wsw + d[e] * wse;
     const float ss = wave_sum(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
     const float nrm = fmaxf(sqrtf(ss), 1e-12f);
-    *o = f32x4_t{r[0] / nrm, r[1] / nrm, r[2] / nrm, r[3] / nrm};
+    *o = f32x4{r[0] / nrm, r[1] / nrm, r[2] / nrm, r[3] / nrm};
 }
 
 // ------------------------------------------------------------------ workspace layout
@@ -440,24 +334,13 @@ __host__ SpLayout sp_layout(int n, const SpDims& d) {
     return L;
 }
 
+// layer `layer` of the blob, with ReLU unless it is one of the two 1x1 heads
 template <int KS, bool POOL>
-hipError_t launch_conv(int n, const float* in, int Hi, int Wi, int in_cstride, int in_c0, int Cin, const float* blob,
-                       const __bf16* w3, int layer, float* out, int out_cstride, int out_c0, int Cout,
-                       hipStream_t stream) {
-    ConvArgs a;
-    a.in = in; a.Hi = Hi; a.Wi = Wi; a.in_cstride = in_cstride; a.in_c0 = in_c0; a.Cin = Cin;
-    a.w = blob + sp_layer_offset(layer);
-    a.cout_pad = kSp[layer].cout_pad;
-    a.bias = a.w + (size_t)kSp[layer].k * kSp[layer].k * kSp[layer].cin * a.cout_pad;
-    a.out = out; a.out_cstride = out_cstride; a.out_c0 = out_c0; a.Cout = Cout; a.relu = 1;
-    a.tiles_x = (Wi + 31) / 32;
-    a.tiles_y = (Hi + conv3_rows(KS) - 1) / conv3_rows(KS);
-    // pooled rows only (MaxPool2d floors; an odd last conv row is dropped): conv3_rp pooled rows per tile
-    if (POOL) a.tiles_y = (Hi / 2 + conv3_rp(KS) - 1) / conv3_rp(KS);
-    if (a.tiles_x == 0 || a.tiles_y == 0) return hipSuccess;
-    const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * n), (unsigned)((Cout + 63) / 64));
-    hipLaunchKernelGGL((conv3_kernel<KS, POOL>), grid, dim3(conv3_threads(KS)), 0, stream, a, w3 + sp_w3_offset(layer));
-    return hipGetLastError();
+hipError_t sp_conv(int n, const float* in, int Hi, int Wi, int in_cstride, int in_c0, const float* blob,
+                   const __bf16* w3, int layer, float* out, int out_cstride, int Cout, hipStream_t stream) {
+    return conv3_launch<KS, POOL>(n, in, Hi, Wi, in_cstride, in_c0, kSp[layer].cin, blob + sp_layer_offset(layer),
+                                  kSp[layer].cout_pad, w3 + sp_w3_offset(layer), out, out_cstride, 0, Cout, KS == 3,
+                                  stream);
 }
 
 }  // namespace
@@ -497,12 +380,11 @@ int gtsfm_superpoint_batched(const uint8_t* d_images, const uint8_t* d_masks, in
     const float* blob = d_weights;
     __bf16* w3 = (__bf16*)(ws + L.w3);
     {
-        size_t most = 0;
+        Conv3SplitJob jobs[kSpLayers - 1];
         for (int l = 1; l < kSpLayers; ++l)
-            most = std::max(most, (size_t)kSp[l].k * kSp[l].k * kSp[l].cin * kSp[l].cout_pad);
-        hipLaunchKernelGGL(sp_split_weights_kernel, dim3((unsigned)((most + 255) / 256), kSpLayers - 1), dim3(256), 0,
-                           stream, blob, w3);
-        GTSFM_CHECK_HIP(hipGetLastError());
+            jobs[l - 1] = {blob + sp_layer_offset(l), w3 + sp_w3_offset(l), kSp[l].k * kSp[l].k, kSp[l].cin,
+                           kSp[l].cout_pad};
+        GTSFM_CHECK_HIP(conv3_split_weights(jobs, kSpLayers - 1, stream));
     }
     // shared encoder (superpoint.py:147-158)
     {
@@ -511,31 +393,18 @@ int gtsfm_superpoint_batched(const uint8_t* d_images, const uint8_t* d_masks, in
                            W, C, blob + sp_layer_offset(L1A), buf0);
         GTSFM_CHECK_HIP(hipGetLastError());
     }
-    GTSFM_CHECK_HIP((launch_conv<3, true>(n, buf0, d.H, d.W, 64, 0, 64, blob, w3, L1B, buf1, 64, 0, 64, stream)));
-    GTSFM_CHECK_HIP((launch_conv<3, false>(n, buf1, d.H2, d.W2, 64, 0, 64, blob, w3, L2A, buf0, 64, 0, 64, stream)));
-    GTSFM_CHECK_HIP((launch_conv<3, true>(n, buf0, d.H2, d.W2, 64, 0, 64, blob, w3, L2B, buf1, 64, 0, 64, stream)));
-    GTSFM_CHECK_HIP((launch_conv<3, false>(n, buf1, d.H4, d.W4, 64, 0, 64, blob, w3, L3A, buf0, 128, 0, 128, stream)));
-    GTSFM_CHECK_HIP((launch_conv<3, true>(n, buf0, d.H4, d.W4, 128, 0, 128, blob, w3, L3B, buf1, 128, 0, 128, stream)));
-    GTSFM_CHECK_HIP((launch_conv<3, false>(n, buf1, d.H8, d.W8, 128, 0, 128, blob, w3, L4A, buf0, 128, 0, 128, stream)));
-    GTSFM_CHECK_HIP((launch_conv<3, false>(n, buf0, d.H8, d.W8, 128, 0, 128, blob, w3, L4B, buf1, 128, 0, 128, stream)));
-    // heads: [convPa | convDa] in one 3x3 (128 -> 512), then the two 1x1s (superpoint.py:161-162, 190-191)
-    GTSFM_CHECK_HIP((launch_conv<3, false>(n, buf1, d.H8, d.W8, 128, 0, 128, blob, w3, LHEAD, buf0, 512, 0, 512, stream)));
-    // convPb: no ReLU; convDb: no ReLU
-    auto conv1x1 = [&](int layer, int in_c0, float* out, int out_cstride, int Cout) -> hipError_t {
-        ConvArgs a;
-        a.in = buf0; a.Hi = d.H8; a.Wi = d.W8; a.in_cstride = 512; a.in_c0 = in_c0; a.Cin = 256;
-        a.w = blob + sp_layer_offset(layer);
-        a.cout_pad = kSp[layer].cout_pad;
-        a.bias = a.w + (size_t)256 * a.cout_pad;
-        a.out = out; a.out_cstride = out_cstride; a.out_c0 = 0; a.Cout = Cout; a.relu = 0;
-        a.tiles_x = (d.W8 + 31) / 32;
-        a.tiles_y = (d.H8 + conv3_rows(1) - 1) / conv3_rows(1);
-        const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * n), (unsigned)((Cout + 63) / 64));
-        hipLaunchKernelGGL((conv3_kernel<1, false>), grid, dim3(conv3_threads(1)), 0, stream, a, w3 + sp_w3_offset(layer));
-        return hipGetLastError();
-    };
-    GTSFM_CHECK_HIP(conv1x1(LPB, 0, logits, 128, 65));
-    GTSFM_CHECK_HIP(conv1x1(LDB, 256, buf1, 256, 256));
+    GTSFM_CHECK_HIP((sp_conv<3, true>(n, buf0, d.H, d.W, 64, 0, blob, w3, L1B, buf1, 64, 64, stream)));
+    GTSFM_CHECK_HIP((sp_conv<3, false>(n, buf1, d.H2, d.W2, 64, 0, blob, w3, L2A, buf0, 64, 64, stream)));
+    GTSFM_CHECK_HIP((sp_conv<3, true>(n, buf0, d.H2, d.W2, 64, 0, blob, w3, L2B, buf1, 64, 64, stream)));
+    GTSFM_CHECK_HIP((sp_conv<3, false>(n, buf1, d.H4, d.W4, 64, 0, blob, w3, L3A, buf0, 128, 128, stream)));
+    GTSFM_CHECK_HIP((sp_conv<3, true>(n, buf0, d.H4, d.W4, 128, 0, blob, w3, L3B, buf1, 128, 128, stream)));
+    GTSFM_CHECK_HIP((sp_conv<3, false>(n, buf1, d.H8, d.W8, 128, 0, blob, w3, L4A, buf0, 128, 128, stream)));
+    GTSFM_CHECK_HIP((sp_conv<3, false>(n, buf0, d.H8, d.W8, 128, 0, blob, w3, L4B, buf1, 128, 128, stream)));
+    // heads: [convPa | convDa] in one 3x3 (128 -> 512), then the two 1x1s (superpoint.py:161-162, 190-191): convPb on
+    // channels 0..255 -> 65 logits, convDb on channels 256..511 -> the descriptor map; no ReLU after either
+    GTSFM_CHECK_HIP((sp_conv<3, false>(n, buf1, d.H8, d.W8, 128, 0, blob, w3, LHEAD, buf0, 512, 512, stream)));
+    GTSFM_CHECK_HIP((sp_conv<1, false>(n, buf0, d.H8, d.W8, 512, 0, blob, w3, LPB, logits, 128, 65, stream)));
+    GTSFM_CHECK_HIP((sp_conv<1, false>(n, buf0, d.H8, d.W8, 512, 256, blob, w3, LDB, buf1, 256, 256, stream)));
     // dense scores + NMS
     float* S = (float*)(ws + L.maps);
     float* P = S + L.map_floats;
@@ -570,12 +439,13 @@ int gtsfm_superpoint_batched(const uint8_t* d_images, const uint8_t* d_masks, in
     int* rowoff = (int*)(ws + L.rowoff);
     int* cidx = (int*)(ws + L.cand_idx);
     float* cscore = (float*)(ws + L.cand_score);
-    hipLaunchKernelGGL(row_count_kernel, dim3(d.Hs, n), dim3(kRowThreads), 0, stream, T, d.Hs, d.Ws,
+    hipLaunchKernelGGL(row_count_kernel, dim3(d.Hs, n), dim3(kScanThreads), 0, stream, T, d.Hs, d.Ws,
                        keypoint_threshold, remove_borders, d_masks, H, W, rowcnt);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(n), dim3(kRowThreads), 0, stream, rowcnt, d.Hs, rowoff, ndet);
-    hipLaunchKernelGGL(row_emit_kernel, dim3(d.Hs, n), dim3(kRowThreads), 0, stream, T, d.Hs, d.Ws,
+    hipLaunchKernelGGL(image_excl_scan_kernel, dim3(n), dim3(kScanThreads), 0, stream, (const int*)rowcnt, d.Hs, rowoff,
+                       ndet);
+    hipLaunchKernelGGL(row_emit_kernel, dim3(d.Hs, n), dim3(kScanThreads), 0, stream, T, d.Hs, d.Ws,
                        keypoint_threshold, remove_borders, d_masks, H, W, rowoff, L.cap, cidx, cscore);
-    hipLaunchKernelGGL(topk_select_kernel, dim3(n), dim3(kTopThreads), 0, stream, cidx, cscore, L.cap, ndet, max_kpts,
+    hipLaunchKernelGGL(topk_select_kernel, dim3(n), dim3(kScanThreads), 0, stream, cidx, cscore, L.cap, ndet, max_kpts,
                        d.Ws, d_xy, d_scores, d_count);
     hipLaunchKernelGGL(desc_sample_kernel, dim3(max_kpts, n), dim3(64), 0, stream, buf1, d.H8, d.W8, d_xy, d_count,
                        max_kpts, d_desc);

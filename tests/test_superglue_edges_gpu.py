@@ -205,8 +205,8 @@ def test_entry_point_checks():
 def test_zero_count_side():
     """A pair with an empty side handed straight to device.superglue_match (SuperGlueMatcher.match_batch filters such
     pairs on the host; the entry point does not need to). With m = 0 or n = 0 every index in sk_init_kernel,
-    sk_pass_kernel, sk_vmerge_kernel, sk_rowmax_kernel, sk_colmax_kernel and sg_emit_kernel stays inside rows 0..m and
-    columns 0..n of the pair's (kmax + 1)^2 block: the score GEMM and the argmax loops run no iteration, the dustbin
+    sk_pass_kernel, sk_vmerge_kernel, assign_rowmax_kernel, assign_colmax_kernel and sg_emit_kernel stays inside rows
+    0..m and columns 0..n of the pair's (kmax + 1)^2 block: the score GEMM and the argmax loops run no iteration, the dustbin
     row / column is the only one read, and sg_emit_kernel reads idx0 / idx1 only when i < m and n > 0. (sk_norm(0, 0)
     is +inf, so a pair empty on both sides would carry NaN in u and v, which index nothing.) The empty pairs give
     count 0 and zero scores, and the pair beside them is bit for bit what it is alone."""
